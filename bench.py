@@ -2,22 +2,29 @@
 """Headline benchmark: img/s of the full G+D StyleGAN training iteration (optimize_discriminator +
 optimize_generator: logistic loss + R1, both Adam steps, grad clip, EMA) on synthetic data, on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run, one rank per GPU)
 
 Workload (BASELINE.json `metric` / configs[2..3]): FFHQ-1024 model (8 mapping layers, no truncation), progressive
 depth index 8 (1024x1024), batch 4 per GPU, alpha 0.5 (fade-in active: both branches live), bf16 activations with
 fp32 accumulation / parameters.  Random-init weights, synthetic N(0,1) latents and images.
 
-The LAST stdout line is ONE compact JSON object (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, a scalar `b32` block);
-the full record with every table goes to gpurun_out/bench_detail.json (`--detail-file`).  `roofline` is measured live with HIP events around every launch of the dominant kernel (the
+A plain run does only what the headline figure needs: set-up (model, input ring, graph capture), W warm-up
+steps, K timed steps, and ONE JSON line, the LAST line of stdout (`value` img/s, `ms_per_step` = time of one timed step).
+`--dump-outputs DIR` then writes what the last timed step computed, as DIR/<name>.npy (`step_outputs`): the same arguments give
+the same inputs, so two builds can be compared output for output.  That is why the timed step runs as hipGraph replay on ONE
+stream by default: with the extra streams (`--streams auto|11|01`) the step is not bit-reproducible run to run, and the
+beta_1 = 0 Adam steps amplify last-bit differences into whole updates.
+
+`--full` adds everything else.  The line stays ONE compact JSON object (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`,
+a scalar `b32` block); the full record with every table goes to the file named by `--detail-file`.  `roofline` is measured live with HIP events around every launch of the dominant kernel (the
 instantiation with the largest total time in a surveyed single-stream step), on the launch stream, by the library's own
 per-launch profiler (sgx_prof_*), in a single-stream eager re-run of the timed steps right after the timed region: each
-launch alone on the GPU, the number `rocprofv3 --kernel-trace --stats -- python bench.py --graphs off --streams 00`
-reproduces (profiles/).  `b32` (default invocation, N=1): a second measured block at batch 32 on the one GPU -- the
+launch alone on the GPU, the number `rocprofv3 --kernel-trace --stats -- python bench.py --full --graphs off --streams 00`
+reproduces (profiles/).  `b32` (`--full`, N=1): a second measured block at batch 32 on the one GPU -- the
 configuration BASELINE.json's north-star target is stated on -- with its own throughput and `roofline`.  `cpu_baseline`
 times the CPU oracle (a port of the reference step, oracle/stylegan_oracle.py) -- or the reference itself where its
 sources exist -- on this host's cores on a bounded sample (rank 0, N=1 only).  Two short extra blocks follow the
-measured ones in the default invocation (N=1, batch 4; `--no-extras` skips them): `sweep_top_depths` = BASELINE
+measured ones under `--full` (N=1, batch 4; `--no-extras` skips them): `sweep_top_depths` = BASELINE
 configs[4]'s depth indices 6,7,8 at the reference's batch sizes with hipGraph replay (the mode `StyleGAN.train` runs),
 and `ffhq128_fp32_b64` = BASELINE configs[1] as its own bench line from a child process.
 """
@@ -55,10 +62,13 @@ def parse():
     ap.add_argument("--cpu-baseline-timeout", type=float, default=150.0)
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--graphs", default="auto", choices=["auto", "on", "off"],
-                    help="replay each half-iteration as captured hipGraphs (with data parallelism: two graphs around the eager all-reduce)")
-    ap.add_argument("--streams", default="auto", choices=["auto", "11", "01", "00"],
-                    help="extra streams of the step: auxiliary (fake branch) / side (weight gradients); auto = measured on this box")
+    ap.add_argument("--graphs", default=None, choices=["auto", "on", "off"],
+                    help="replay each half-iteration as captured hipGraphs (with data parallelism: two graphs around the eager all-reduce); "
+                         "default: on for the timed step (see --streams), auto for the batch-32 block")
+    ap.add_argument("--streams", default=None, choices=["auto", "11", "01", "00"],
+                    help="extra streams of the step: auxiliary (fake branch) / side (weight gradients); auto = measured on this box.  Default: "
+                         "00 for the timed step -- the only launch structure whose step is bit-reproducible run to run, which the dumped "
+                         "outputs need -- and auto for the batch-32 block")
     ap.add_argument("--dry-run-ranks-on-one-gpu", action="store_true",
                     help="TEST ONLY: every rank on cuda:0 over a gloo group (RCCL refuses two ranks per device): exercises the N>1 "
                          "control flow (calibration votes, sharded step, all-reduce, max-over-ranks timing) on a 1-GPU box; the "
@@ -70,7 +80,7 @@ def parse():
                     help="N=1 only: run the data-parallel code path over an RCCL process group of size 1 (bucketed all-reduce launched for real, "
                          "replay split into [graph | all-reduce | update]) -- measures what that path costs per step on one GPU; not a scaling run")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the two short extra blocks of the default invocation: BASELINE configs[4]'s top depths (6,7,8) replayed, "
+                    help="skip the two short extra blocks of a --full run: BASELINE configs[4]'s top depths (6,7,8) replayed, "
                          "and BASELINE configs[1] (ffhq128, fp32, batch 64) in a child process")
     ap.add_argument("--detail-file", default="gpurun_out/bench_detail.json",
                     help="where the full record (per-layer tables, calibration, sweep rows, the configs[1] block) is written, relative to the repo root")
@@ -82,7 +92,30 @@ def parse():
     ap.add_argument("--sweep-depths", default=None, help="comma-separated depth indices to measure (default: all)")
     ap.add_argument("--sweep-batch-scale", type=float, default=1.0,
                     help="multiply the reference's per-depth batch sizes (its schedule fits an 11 GB card; kept a multiple of 4 where >= 4)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: the kernel survey and roofline, the batch-32 block, the two extra "
+                         "blocks, the CPU baseline and the detail file (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (both losses, seeded samples of the updated "
+                         "parameters) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.layer_table and not a.full:
+        ap.error("--layer-table comes from the kernel survey of a --full run")
+    if a.dump_outputs and a.sweep:
+        ap.error("--dump-outputs dumps the timed headline step; --sweep has none")
+    return a
+
+
+def plan(a, world):
+    """What a run measures besides its timed steps: nothing unless --full."""
+    headline = a.config == "ffhq1024" and a.dtype == "bf16"
+    return {"kernel_timing": a.full and not a.no_kernel_timing,
+            "b32": a.full and headline and world == 1 and a.batch_per_gpu != 32 and not a.no_b32,
+            "extras": a.full and headline and world == 1 and a.batch_per_gpu == 4 and not a.no_extras,
+            "cpu_baseline": a.full and world == 1 and not a.no_cpu_baseline,
+            "detail_file": a.full and not a.no_detail_file}
 
 
 # reference config.py:37-42 (cfg.sched): per-depth batch sizes for resolutions 4 .. 1024 and the fade-in share of a depth's iterations
@@ -192,7 +225,7 @@ def extra_ffhq128_fp32_b64(timeout_s=150.0):
     process (own model, own dtype), embedded without its evidence text."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", "ffhq128", "--dtype", "fp32", "--batch-per-gpu", "64",
-           "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--no-detail-file"]
+           "--steps", "5", "--warmup", "2", "--graphs", "auto", "--streams", "auto", "--full", "--no-cpu-baseline", "--no-extras", "--no-detail-file"]
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
@@ -328,9 +361,11 @@ def make_stylegan(a, cfg, dev, dp):
 RING = 4                                                     # pre-generated synthetic batches resident in HBM ("a ring of 4")
 
 
-def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_opts, layer_table=None, traffic_ok=False):
-    """One measured block: launch-structure calibration, warm-up, surveyed step (single stream), timed region, roofline of the
-    dominant kernel on ONE stream.  -> dict (the fields of the JSON line that depend on the batch size)."""
+def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_opts, kernel_timing=False, layer_table=None,
+            traffic_ok=False, keep_outputs=False):
+    """One measured block: launch-structure calibration, warm-up, surveyed step (single stream, `kernel_timing`), timed region,
+    roofline of the dominant kernel on ONE stream (`kernel_timing`).  -> dict (the fields of the JSON line that depend on the batch
+    size; `keep_outputs`: + "outputs", what the last timed step computed, see `step_outputs`)."""
     from stylegan.pytorch_amd import native
     res, depth = cfg["resolution"], cfg["depth"]
     gen = torch.Generator(device=dev); gen.manual_seed(1234 + rank)
@@ -341,8 +376,7 @@ def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_
 
     def step(i):
         z, x = lats[i % RING], reals[i % RING]
-        sg.optimize_discriminator(z, x, depth, a.alpha)
-        sg.optimize_generator(z, x, depth, a.alpha)
+        return sg.optimize_discriminator(z, x, depth, a.alpha), sg.optimize_generator(z, x, depth, a.alpha)
 
     def barrier():
         if world > 1:
@@ -428,7 +462,7 @@ def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_
     # Roofline leg, part 1 (untimed): ONE surveyed single-stream step with the library's per-launch profiler on every kernel, to
     # find the dominant kernel (largest total time) and the per-layer table.
     survey = None
-    if not a.no_kernel_timing:
+    if kernel_timing:
         def do_survey():
             step(warmup)                                     # (the mode switch re-packs nothing; one untimed step settles allocations)
             torch.cuda.synchronize()
@@ -456,13 +490,14 @@ def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_
     barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        step(warmup + 3 + i)
+        losses = step(warmup + 3 + i)
     t_enq = time.perf_counter() - t0                        # host time to enqueue the region (launch-bound if ~= dt)
     torch.cuda.synchronize(); barrier()
     dt = time.perf_counter() - t0
     gc.enable()
     if world > 1:
         dt = max_over_ranks([dt])[0]
+    outputs = step_outputs(sg, losses) if keep_outputs else None   # before the roofline re-run moves the parameters on
 
     roof = None
     if survey is not None:
@@ -558,8 +593,37 @@ def measure(sg, a, cfg, dev, B, steps, warmup, rank, world, want_graphs, stream_
         out["executed_frac_of_mfma_peak"] = executed_flops / (dt / steps) / PEAK[a.dtype]
         out["executed_gflop_per_img"] = executed_flops / B / 1e9
         out["roofline"] = roof
+    if outputs is not None:
+        out["outputs"] = outputs
     del reals, lats
     return out
+
+
+DUMP_SAMPLE = 1 << 21    # parameters kept per network by --dump-outputs (float32: 8 MB each, 24 MB in all)
+DUMP_LIMIT = 64 << 20
+
+
+def step_outputs(sg, losses):
+    """What a caller of the timed step holds after it: the two losses it returns, and the parameters it updated in place
+    (generator, discriminator, EMA generator), each network's parameters flattened in `named_parameters` order -- a fixed sample
+    of DUMP_SAMPLE of them (indices drawn from seed 0, sorted) where the network has more.  -> {name: numpy array}"""
+    import numpy as np
+    out = {"d_loss": np.float64(float(losses[0])), "g_loss": np.float64(float(losses[1]))}
+    for name, net in (("gen_params", sg.gen), ("dis_params", sg.dis), ("gen_ema_params", sg.gen_shadow)):
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in net.named_parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[name] = flat.cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, out_dir):
+    import numpy as np
+    assert sum(v.nbytes for v in outputs.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 LINE_LIMIT = 4096        # the driver keeps ~8 KB of stdout: the LAST line must sit wholly inside it (round 5's 21 KB line did not parse)
@@ -715,20 +779,23 @@ def main():
                           "worst_depth": {"depth": worst["depth"], "frac_of_mfma_peak": worst["frac_of_mfma_peak"]},
                           "sweep": rows}))
         return
-    want_graphs = [False] if a.graphs == "off" else ([True] if a.graphs == "on" else [False, True])
-    stream_opts = {"auto": [(True, True), (False, True), (False, False)], "11": [(True, True)], "01": [(False, True)], "00": [(False, False)]}[a.streams]
+    graphs, streams = a.graphs or "on", a.streams or "00"
+    want_graphs = [False] if graphs == "off" else ([True] if graphs == "on" else [False, True])
+    stream_opts = {"auto": [(True, True), (False, True), (False, False)], "11": [(True, True)], "01": [(False, True)], "00": [(False, False)]}[streams]
     headline = a.config == "ffhq1024" and a.dtype == "bf16"
-    blk = measure(sg, a, cfg, dev, B, a.steps, a.warmup, rank, world, want_graphs, stream_opts, layer_table=a.layer_table,
-                  traffic_ok=headline and B in (4, 32))
+    todo = plan(a, world)
+    blk = measure(sg, a, cfg, dev, B, a.steps, a.warmup, rank, world, want_graphs, stream_opts, kernel_timing=todo["kernel_timing"],
+                  layer_table=a.layer_table, traffic_ok=headline and B in (4, 32), keep_outputs=bool(a.dump_outputs) and rank == 0)
+    outputs = blk.pop("outputs", None)
     b32 = None
-    if headline and world == 1 and B != 32 and not a.no_b32:
+    if todo["b32"]:
         # second measured block: the north-star target configuration (BASELINE.json: >= 40 % of the bf16 MFMA peak at batch 32
         # on ONE MI355X), same model, same weights object, 8 timed steps.  Stream launches only: at 80 ms per step the host is
         # never the limit, and a captured graph of this size would hold a second private copy of every activation.
         torch.cuda.synchronize(); torch.cuda.empty_cache()
         sg._step_graphs.clear()
         b32 = measure(sg, a, cfg, dev, 32, a.b32_steps, 2, rank, world, [False],
-                      [(True, True), (False, False)] if a.streams == "auto" else stream_opts,
+                      [(True, True), (False, False)] if a.streams in (None, "auto") else stream_opts, kernel_timing=todo["kernel_timing"],
                       layer_table=(a.layer_table + ".b32.tsv") if a.layer_table else None, traffic_ok=True)
 
     if rank == 0:
@@ -751,13 +818,15 @@ def main():
         if b32 is not None:
             b32["config"] = {"workload": f"{a.config}: same model, batch 32 on one GPU (the north-star target configuration)"}
             out["b32"] = b32
-        if headline and world == 1 and not a.no_extras and B == 4:
+        if todo["extras"]:
             out["sweep_top_depths"] = extra_sweep_top_depths(sg, a, cfg, dev)
             out["ffhq128_fp32_b64"] = extra_ffhq128_fp32_b64()
-        if world == 1 and not a.no_cpu_baseline:
+        if todo["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline_subprocess(a.config, a.cpu_baseline_timeout)
-        detail = None if a.no_detail_file else write_detail(out, os.path.join(ROOT, a.detail_file))
+        detail = write_detail(out, os.path.join(ROOT, a.detail_file)) if todo["detail_file"] else None
         line = compact_line(out, detail)
+        if outputs is not None:
+            write_outputs(outputs, a.dump_outputs)
     # The JSON line must be the LAST line of the job's stdout.  RCCL prints its version banner through C stdio, which is fully buffered
     # when stdout is a pipe: left alone it comes out when the process exits, AFTER Python's own output (seen with --rccl-group-of-one:
     # `tail -1` was "Librccl path : ...").  So: tear the group down, flush C stdio on every rank, let the other ranks' processes end,

@@ -1,10 +1,13 @@
 """bench.py's host-side contract, checked without a GPU: the defaults the driver runs with, the extra blocks' child command (it must not
-recurse into extras or time the CPU leg again), and the per-depth constants of the progressive sweep (reference config.py:40-41)."""
+recurse into extras or time the CPU leg again), what a plain and a `--full` run measure, the dumped outputs, and the per-depth constants of
+the progressive sweep (reference config.py:40-41)."""
 import json
 import os
 import subprocess
 import sys
 import types
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,6 +20,53 @@ def test_defaults_are_the_headline_workload(monkeypatch):
     assert (a.gpus, a.config, a.dtype, a.batch_per_gpu) == (1, "ffhq1024", "bf16", 4)
     assert a.steps >= 10 and a.warmup >= 1
     assert not a.no_extras and not a.no_b32 and not a.no_cpu_baseline and not a.sweep
+    assert not a.full and a.dump_outputs is None
+    assert a.graphs is None and a.streams is None                             # the timed step: replay on one stream (bit-reproducible)
+
+
+def test_a_plain_run_measures_only_the_headline_and_full_measures_what_the_default_did(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2
+    assert not any(bench.plan(a, 1).values())
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert all(bench.plan(a, 1).values())
+    todo = bench.plan(a, 2)                                                   # N > 1: survey + detail file, no single-GPU blocks
+    assert todo["kernel_timing"] and todo["detail_file"] and not (todo["b32"] or todo["extras"] or todo["cpu_baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-kernel-timing", "--no-b32", "--no-extras", "--no-cpu-baseline",
+                                      "--no-detail-file"])
+    assert not any(bench.plan(bench.parse(), 1).values())
+
+
+def test_parse_rejects_what_a_run_cannot_honour(monkeypatch):
+    for argv in (["--steps", "0"], ["--layer-table", "t.tsv"], ["--sweep", "--dump-outputs", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_dumped_outputs_are_the_losses_and_a_fixed_sample_of_every_updated_network(tmp_path, monkeypatch):
+    import numpy as np
+    torch = bench.torch
+
+    def net(seed, n):
+        torch.manual_seed(seed)
+        return torch.nn.Sequential(torch.nn.Linear(n, n), torch.nn.Linear(n, 3))
+    sg = types.SimpleNamespace(gen=net(1, 40), dis=net(2, 8), gen_shadow=net(3, 40))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 500)                            # gen: 1763 values -> sampled; dis: 99 -> whole
+    out = bench.step_outputs(sg, (1.5, -2.25))
+    assert sorted(out) == ["d_loss", "dis_params", "g_loss", "gen_ema_params", "gen_params"]
+    assert out["d_loss"] == 1.5 and out["g_loss"] == -2.25 and out["d_loss"].dtype == np.float64
+    flat = torch.cat([p.detach().reshape(-1) for p in sg.dis.parameters()]).numpy()
+    assert np.array_equal(out["dis_params"], flat)
+    assert out["gen_params"].shape == (500,) and out["gen_params"].dtype == np.float32
+    again = bench.step_outputs(sg, (1.5, -2.25))
+    assert all(np.array_equal(out[k], again[k]) for k in out)                 # the same sample every run
+    bench.write_outputs(out, str(tmp_path / "d"))
+    for k, v in out.items():
+        assert np.array_equal(np.load(tmp_path / "d" / (k + ".npy")), v)
+    assert 3 * bench.DUMP_SAMPLE * 4 + 16 <= bench.DUMP_LIMIT == 64 << 20
 
 
 def test_sweep_constants_follow_the_reference_schedule():
@@ -38,8 +88,9 @@ def test_the_ffhq128_block_is_a_bounded_child_that_cannot_recurse(monkeypatch):
     out = bench.extra_ffhq128_fp32_b64()
     cmd = seen["cmd"]
     assert cmd[0] == sys.executable and os.path.basename(cmd[1]) == "bench.py"
-    for flag in ("--no-extras", "--no-cpu-baseline"):
+    for flag in ("--full", "--no-extras", "--no-cpu-baseline"):
         assert flag in cmd
+    assert cmd[cmd.index("--graphs") + 1] == "auto" and cmd[cmd.index("--streams") + 1] == "auto"
     assert cmd[cmd.index("--config") + 1] == "ffhq128" and cmd[cmd.index("--dtype") + 1] == "fp32" and cmd[cmd.index("--batch-per-gpu") + 1] == "64"
     assert seen["kw"].get("timeout", 0) > 0
     assert out["value"] == 1.0 and out["roofline"] == {"bound": "mfma"} and "evidence" not in out and "wall_s" in out

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-6 evidence in one GPU-box session.   usage: tools/gpu_final6.sh <tag> [test|notest] [ab]
-#   smoke; the default bench line (headline batch 4 + the batch-32 block + cpu_baseline) and its layer tables; single-stream bench lines at
+#   smoke; the --full bench line (headline batch 4 + the batch-32 block + cpu_baseline) and its layer tables; single-stream bench lines at
 #   batch 4 and 32 (per-kernel times without stream overlap) + step budgets; and for BOTH batch sizes: rocprofv3 --kernel-trace --stats,
 #   one SQ counter pass, two HBM traffic passes of the single-stream step.  `test`: the whole -m gpu suite first.
 # Every JSON / text artefact gets the box id and the commit the snapshot was made from (tools/.evidence_commit, written by the caller).
@@ -28,9 +28,9 @@ if [ "$2" = "test" ]; then
   grep -aE "passed|failed" $O/pytest.log | tail -2; stamp_txt $O/pytest.log
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-echo "== bench default (b4 + b32 blocks, cpu baseline)"; timeout 900 python bench.py --layer-table $O/layers_b4.tsv 2>$O/bench_default.err | tail -1 > $O/bench_default.json; stamp_json $O/bench_default.json; cp gpurun_out/bench_detail.json $O/bench_default_detail.json 2>/dev/null; wc -c < $O/bench_default.json; cut -c1-260 $O/bench_default.json
-echo "== bench b4 single stream"; timeout 400 python bench.py --no-b32 --no-extras --no-cpu-baseline --graphs off --streams 00 --layer-table $O/layers_b4_single.tsv 2>/dev/null | tail -1 > $O/bench_b4_single.json; stamp_json $O/bench_b4_single.json; cut -c1-200 $O/bench_b4_single.json
-echo "== bench b32 single stream"; timeout 400 python bench.py --batch-per-gpu 32 --steps 8 --warmup 2 --no-cpu-baseline --graphs off --streams 00 --layer-table $O/layers_b32_single.tsv 2>/dev/null | tail -1 > $O/bench_b32_single.json; stamp_json $O/bench_b32_single.json; cut -c1-200 $O/bench_b32_single.json
+echo "== bench default (b4 + b32 blocks, cpu baseline)"; timeout 900 python bench.py --full --layer-table $O/layers_b4.tsv --detail-file $O/bench_default_detail.json 2>$O/bench_default.err | tail -1 > $O/bench_default.json; stamp_json $O/bench_default.json; wc -c < $O/bench_default.json; cut -c1-260 $O/bench_default.json
+echo "== bench b4 single stream"; timeout 400 python bench.py --full --no-b32 --no-extras --no-cpu-baseline --graphs off --streams 00 --layer-table $O/layers_b4_single.tsv 2>/dev/null | tail -1 > $O/bench_b4_single.json; stamp_json $O/bench_b4_single.json; cut -c1-200 $O/bench_b4_single.json
+echo "== bench b32 single stream"; timeout 400 python bench.py --full --batch-per-gpu 32 --steps 8 --warmup 2 --no-cpu-baseline --graphs off --streams 00 --layer-table $O/layers_b32_single.tsv 2>/dev/null | tail -1 > $O/bench_b32_single.json; stamp_json $O/bench_b32_single.json; cut -c1-200 $O/bench_b32_single.json
 python tools/step_budget.py $O/layers_b4_single.tsv > $O/step_budget_b4.txt 2>&1; python tools/step_budget.py $O/layers_b32_single.tsv > $O/step_budget_b32.txt 2>&1
 for f in $O/layers_*.tsv $O/step_budget_*.txt; do stamp_txt $f; done
 if [ "$3" = "ab" ]; then
@@ -39,7 +39,7 @@ if [ "$3" = "ab" ]; then
   echo "== A/B on this box, default bench line, interleaved: [all off] = the round's switches off ($OFF1 $OFF2); [session 1] = only the second session's off ($OFF2); [on] = defaults"
   for i in 1 2; do for v in alloff session1 on; do
     if [ $v = alloff ]; then e="$OFF1 $OFF2"; elif [ $v = session1 ]; then e="$OFF2"; else e="SGX_AB_DUMMY=1"; fi
-    env $e timeout 400 python bench.py --no-cpu-baseline --no-extras --steps 30 2>/dev/null | tail -1 | python -c "
+    env $e timeout 400 python bench.py --full --no-cpu-baseline --no-extras --steps 30 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('[$v] b4', round(d['value'], 1), 'img/s', round(d['ms_per_step'], 3), 'ms graphs', d.get('hip_graphs'), 'launches', d.get('library_launches_per_step'), '| b32', round(d['b32']['value'], 1), 'img/s', round(d['b32']['ms_per_step'], 2), 'ms')"

@@ -12,6 +12,6 @@ i=0
 for b in "$@"; do
   i=$((i+1))
   echo "== bench $b"
-  timeout 900 python bench.py $b --layer-table $O/layers_$i.tsv > $O/bench_$i.json 2> $O/bench_$i.err; echo "rc=$?"
+  timeout 900 python bench.py --full $b --layer-table $O/layers_$i.tsv > $O/bench_$i.json 2> $O/bench_$i.err; echo "rc=$?"
   tail -1 $O/bench_$i.json | cut -c1-330; tail -3 $O/bench_$i.err | cut -c1-300
 done
