@@ -236,6 +236,20 @@ size_t sgx_rgb_wgrad_ws_bytes(size_t npix, int C);
 /* real images at the current depth with the fade-in blend (models/GAN.py:575-586): out = alpha * x + beta *
  * nearest_up2(avgpool2(x)) on fp32 [B][H][W][3] in one pass; ab_dev as in sgx_rgb_out_fade. */
 int sgx_downsample_fade_rgb(const float* x, float* out, int B, int H, int W, float alpha, float beta, const float* ab_dev, void* stream);
+/* DiffAugment (Zhao et al., NeurIPS 2020) of the discriminator's input: fp32 [B][H][W][3] images, policy_bits a subset of
+ * 1 = color, 2 = translation, 4 = cutout, applied in that order; u: DEVICE fp32 [B][7] uniform draws in [0,1) per image.
+ *   color: b = u0 - 0.5, s = 2 u1, c = u2 + 0.5;  L x = c s (x - m_x) + c (m_x - M_x) + M_x (m_x: mean over the 3 channels of a
+ *          pixel, M_x: mean over the image), the DiffAugment brightness / saturation / contrast chain in closed form.
+ *   translation: sh = int(H/8 + 0.5), tx = min(floor(u3 (2 sh + 1)), 2 sh) - sh (ty from u4 and W), the product in fp32;
+ *          y[i][j] = x[i + tx][j + ty] inside the image, 0 outside.
+ *   cutout: ch = int(H/2 + 0.5), ox = min(floor(u5 (H + 1 - ch%2)), H - ch%2) (oy from u6 and W); rows [ox - ch/2, ox - ch/2 + ch) x
+ *          the same columns of the output are 0.
+ * adjoint = 0: y = Mask(Shift(L x + b)) (b only if with_bias);  adjoint = 1: y = L(Shift^T(Mask x)) (the transpose of the linear part).
+ * Gathers only (x != y), no atomics: bit-reproducible.  ws: sgx_diffaug_ws_bytes(B, H, W) bytes, read only when color is on (the
+ * per-image sums).  Replaces DiffAugment's rand_brightness / rand_saturation / rand_contrast / rand_translation / rand_cutout.   */
+size_t sgx_diffaug_ws_bytes(int B, int H, int W);
+int sgx_diffaug(const float* x, float* y, const float* u, int B, int H, int W, int policy_bits, int adjoint, int with_bias, void* ws,
+                size_t ws_bytes, void* stream);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

@@ -346,8 +346,12 @@ class Discriminator(nn.Module):
 
     def __init__(self, resolution, num_channels=3, conditional=False, n_classes=0, fmap_base=8192, fmap_decay=1.0,
                  fmap_max=512, nonlinearity='lrelu', use_wscale=True, mbstd_group_size=4, mbstd_num_features=1,
-                 blur_filter=None, structure='linear', act_dtype=torch.float32, **kwargs):
+                 blur_filter=None, structure='linear', act_dtype=torch.float32, diffaug_policy="", **kwargs):
         super().__init__()
+        # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
+        # 'color,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
+        self.diffaug_policy = diffaug_policy or ""
+        self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
         if conditional:
             # reference :326-330: the label embedding joins the image as num_channels extra channels of the from_rgb input
             assert n_classes > 0, "Conditional Discriminator requires n_class > 0"
@@ -386,6 +390,16 @@ class Discriminator(nn.Module):
         self.from_rgb = nn.ModuleList(from_rgb)
         self.temporaryDownsampler = lambda x: F.nchw_view(F.call(F.Pool2Fn, F.nhwc(x), 0.25))
 
+    # test hook, after Generator._mixing_override: a [B,7] device tensor of DiffAugment draws used by every D evaluation while set
+    # (instead of fresh torch.rand draws)
+    diffaug_override = None
+
+    def _diffaug(self, img):
+        u = self.diffaug_override
+        if u is None:
+            u = torch.rand(img.shape[0], 7, device=img.device)           # torch's graph-safe generator: fresh draws at every replay
+        return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+
     def prepack(self, depth=None, img_shape=None):
         """Operand packs of every convolution whose weights changed since they were last packed (one launch), plus -- given the
         depth and the NHWC image shape -- the composed from_rgb/conv0 pack of the newest block.  The step calls this BEFORE it forks
@@ -399,6 +413,8 @@ class Discriminator(nn.Module):
     def forward(self, images_in, depth, alpha=1., labels_in=None):
         assert depth < self.depth, "Requested output depth cannot be produced"
         img = F.nhwc(images_in, torch.float32)                              # [B,R,R,3] fp32
+        if self._diffaug_bits and self.training:
+            img = self._diffaug(img)                                        # one draw per D evaluation
         self.prepack(depth, img.shape)                                      # all stale MFMA operand packs: one launch
         dt = self.act_dtype
         if self.conditional:
@@ -838,7 +854,9 @@ class StyleGAN:
     def _graphed(self, kind, noise, real_batch, depth, alpha):
         self._wait_update("d"); self._wait_update("g")          # leftovers of eager calls (the graphs update in line)
         key = (kind, int(depth), tuple(noise.shape), tuple(real_batch.shape), tuple(real_batch.stride()), real_batch.dtype,
-               self.aux_stream, self.param_stream)                     # a captured graph bakes its stream structure in
+               self.aux_stream, self.param_stream,                     # a captured graph bakes its stream structure in
+               self.dis._diffaug_bits, self.dis.training,              # ... and whether (and from where) D's input is augmented
+               None if self.dis.diffaug_override is None else self.dis.diffaug_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)

@@ -129,7 +129,8 @@ def default_cfg():
         "model": {
             "gen": {"latent_size": 512, "mapping_layers": 4, "blur_filter": [1, 2, 1], "truncation_psi": 0.7,
                     "truncation_cutoff": 8},                                                      # :61-67
-            "dis": {"use_wscale": True, "blur_filter": [1, 2, 1]},                                # :72-74
+            "dis": {"use_wscale": True, "blur_filter": [1, 2, 1],                                 # :72-74
+                    "diffaug_policy": ""},            # DiffAugment of D's input, e.g. "color,translation,cutout" ('' = off)
             "g_optim": {"learning_rate": 0.003, "beta_1": 0, "beta_2": 0.99, "eps": 1e-8},        # :79-83
             "d_optim": {"learning_rate": 0.003, "beta_1": 0, "beta_2": 0.99, "eps": 1e-8},        # :88-92
         },

@@ -2278,3 +2278,95 @@ def images_from_uint8(u8, flip=None, out_dtype=torch.float32, layout=None):
 def nchw_view(x_nhwc):
     """Contiguous NHWC -> logical NCHW view (channels_last strides, zero copy)."""
     return x_nhwc.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------------------------------
+# DiffAugment (Zhao et al., NeurIPS 2020) of the discriminator's fp32 NHWC RGB input, ``sgx_diffaug``: A x + b with A linear per
+# image (colour, translation, cutout for the seven draws u[b]).  The chain DiffAugFn -> DiffAugAdjFn -> DiffAugLinFn -> DiffAugAdjFn
+# closes under differentiation, so the R1 penalty's double backward runs through it.
+DIFFAUG_OPS = ("color", "translation", "cutout")          # bit k of the kernels' policy argument: DIFFAUG_OPS[k]
+
+
+def diffaug_policy_bits(policy):
+    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,translation,cutout`` in that (canonical) order,
+    each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
+    if policy is None:
+        return 0
+    if not isinstance(policy, str):
+        raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
+    bits, last = 0, -1
+    for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
+        if name not in DIFFAUG_OPS:
+            raise ValueError(f"unknown DiffAugment op {name!r} in {policy!r} (known: {','.join(DIFFAUG_OPS)})")
+        k = DIFFAUG_OPS.index(name)
+        if k <= last:
+            raise ValueError(f"DiffAugment policy {policy!r}: ops must appear once each, in the order {','.join(DIFFAUG_OPS)}")
+        bits |= 1 << k
+        last = k
+    return bits
+
+
+def _diffaug(x, u, bits, adjoint, with_bias):
+    x, u = _c(x), _c(u)
+    if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
+        raise N.SgxError(f"diffaug: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    B, H, W, _ = x.shape
+    if tuple(u.shape) != (B, 7) or u.dtype != torch.float32 or u.device != x.device:
+        raise N.SgxError(f"diffaug: need fp32 [{B},7] draws on {x.device}, got {tuple(u.shape)} {u.dtype} on {u.device}")
+    y = torch.empty_like(x)
+    L = N.lib()
+    ws, nb = None, 0
+    if bits & 1:
+        nb = L.sgx_diffaug_ws_bytes(B, H, W)
+        ws = N.workspace(nb, x.device)
+    N.check(L.sgx_diffaug(N.ptr(x), N.ptr(y), N.ptr(u), B, H, W, int(bits), int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream()),
+            "sgx_diffaug")
+    return y
+
+
+class DiffAugFn(Function):
+    """y = Mask(Shift(L x + b)) with the draws ``u`` [B,7] (no gradient); backward = the adjoint (DiffAugAdjFn), none when x needs
+    no gradient (the D step's fakes)."""
+
+    @staticmethod
+    def forward(ctx, x, u, bits):
+        ctx.save_for_backward(u)
+        ctx.bits = bits
+        return _diffaug(x, u, bits, False, True)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (u,) = ctx.saved_tensors
+        return _bcall(DiffAugAdjFn, g, u, ctx.bits), None, None
+
+
+class DiffAugAdjFn(Function):
+    """A^T g = L(Shift^T(Mask g)); backward = A without the bias (DiffAugLinFn)."""
+
+    @staticmethod
+    def forward(ctx, g, u, bits):
+        ctx.save_for_backward(u)
+        ctx.bits = bits
+        return _diffaug(g, u, bits, True, False)
+
+    @staticmethod
+    def backward(ctx, gg):
+        (u,) = ctx.saved_tensors
+        return _bcall(DiffAugLinFn, gg, u, ctx.bits), None, None
+
+
+class DiffAugLinFn(Function):
+    """A x = Mask(Shift(L x)) (the linear part of DiffAugFn); backward = DiffAugAdjFn."""
+
+    @staticmethod
+    def forward(ctx, x, u, bits):
+        ctx.save_for_backward(u)
+        ctx.bits = bits
+        return _diffaug(x, u, bits, False, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        (u,) = ctx.saved_tensors
+        return _bcall(DiffAugAdjFn, g, u, ctx.bits), None, None

@@ -76,6 +76,8 @@ SIGNATURES = {
     "sgx_rgb_in_add": (I, [P, P, I, I, F, P, P, Z, I, I, P]),
     "sgx_rgb_out": (I, [P, P, I, I, F, P, P, Z, I, I, P]),
     "sgx_downsample_fade_rgb": (I, [P, P, I, I, I, F, F, P, P]),
+    "sgx_diffaug_ws_bytes": (Z, [I, I, I]),
+    "sgx_diffaug": (I, [P, P, P, I, I, I, I, I, I, P, Z, P]),
     "sgx_rgb_out_fade": (I, [P, P, I, I, F, P, P, F, F, P, P, I, I, I, I, I, P]),
     "sgx_rgb_wgrad_ws_bytes": (Z, [Z, I]),
     "sgx_rgb_wgrad": (I, [P, P, P, I, I, F, P, Z, Z, I, I, P]),

@@ -1,0 +1,119 @@
+"""DiffAugment probe (csrc/diffaug.hip): what the augmentation costs on the MI355X.
+
+  python tools/diffaug_probe.py --kernels [--batch 32 --res 1024]
+      launches the forward (with bias) and the adjoint of policy color,translation,cutout a few times on one image batch; run it under
+      ``rocprofv3 --kernel-trace --stats -d DIR -o diffaug -- python tools/diffaug_probe.py --kernels`` for per-kernel times.
+  python tools/diffaug_probe.py --stats DIR/.../diffaug_kernel_stats.csv [--batch 32 --res 1024]
+      per-kernel mean time from that run and the algorithmic bytes / time (sum pass: 12 B per pixel read; apply: 12 B read + 12 B written).
+  python tools/diffaug_probe.py --ab [--batches 4,32 --repeats 4 --steps 8]
+      step time at ffhq1024, bf16, hipGraph replay (bench.make_stylegan), policy off vs color,translation,cutout, interleaved on ONE
+      StyleGAN object (each policy has its own captured graphs) -- prints one JSON line.
+"""
+import argparse
+import csv
+import json
+import os
+import socket
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402
+
+POLICY = "color,translation,cutout"
+
+
+def kernels(a):
+    from stylegan.pytorch_amd import functional as F
+    B, R = a.batch, a.res
+    x = torch.randn(B, R, R, 3, device="cuda")
+    u = torch.rand(B, 7, device="cuda")
+    bits = F.diffaug_policy_bits(POLICY)
+    for _ in range(a.iters):
+        y = F._diffaug(x, u, bits, False, True)
+        F._diffaug(y, u, bits, True, False)
+    torch.cuda.synchronize()
+
+
+def stats(a):
+    px = a.batch * a.res * a.res
+    bytes_of = {"diffaug_sum_kernel": 12.0 * px, "diffaug_apply_kernel": 24.0 * px}
+    rows = []
+    with open(a.stats) as f:
+        for r in csv.DictReader(f):
+            name = r["Name"]
+            base = next((k for k in bytes_of if k in name), None)
+            if base is None:
+                continue
+            ns = float(r["AverageNs"])
+            rows.append(dict(kernel=name, calls=int(r["Calls"]), mean_us=round(ns / 1e3, 2),
+                             algorithmic_TBps=round(bytes_of[base] / ns / 1e3, 3)))
+    print(json.dumps(dict(batch=a.batch, res=a.res, kernels=rows)))
+
+
+def ab(a):
+    import bench
+    from stylegan.pytorch_amd import functional as F
+    cfg = bench.CONFIGS["ffhq1024"]
+    dev = torch.device("cuda:0")
+    args = argparse.Namespace(dtype="bf16", graphs="on", alpha=0.5)
+    out = dict(box=socket.gethostname(), commit=a.commit, config="ffhq1024", dtype="bf16", graphs=True, policy=POLICY, blocks=[])
+    for B in [int(b) for b in a.batches.split(",")]:
+        sg = bench.make_stylegan(args, cfg, dev, None)
+        res, depth = cfg["resolution"], cfg["depth"]
+        g = torch.Generator(device=dev); g.manual_seed(1234)
+        reals = [torch.randn(B, res, res, 3, device=dev, generator=g).permute(0, 3, 1, 2) for _ in range(2)]
+        lats = [torch.randn(B, 512, device=dev, generator=g) for _ in range(2)]
+
+        def run(policy, n):
+            sg.dis.diffaug_policy, sg.dis._diffaug_bits = policy, F.diffaug_policy_bits(policy)
+            torch.cuda.synchronize(); t = time.perf_counter()
+            for i in range(n):
+                sg.optimize_discriminator(lats[i % 2], reals[i % 2], depth, 0.5)
+                sg.optimize_generator(lats[i % 2], reals[i % 2], depth, 0.5)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n * 1e3
+
+        for p in ("", POLICY):
+            run(p, 4)                                                # 2 eager calls + capture + a replay per half-iteration and policy
+        times = {"off": [], "on": []}
+        for r in range(a.repeats):
+            order = [("off", ""), ("on", POLICY)] if r % 2 == 0 else [("on", POLICY), ("off", "")]
+            for key, p in order:
+                times[key].append(run(p, a.steps))
+        off, on = min(times["off"]), min(times["on"])
+        out["blocks"].append(dict(batch=B, ms_per_step_off=[round(t, 3) for t in times["off"]], ms_per_step_on=[round(t, 3) for t in times["on"]],
+                                  best_off=round(off, 3), best_on=round(on, 3), slowdown_pct=round(100 * (on / off - 1), 2)))
+        del sg
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--stats", default=None)
+    ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--res", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--batches", default="4,32")
+    ap.add_argument("--repeats", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--commit", default=os.environ.get("SGX_COMMIT", ""))
+    a = ap.parse_args()
+    if a.stats:
+        stats(a)
+    elif a.kernels:
+        kernels(a)
+    elif a.ab:
+        ab(a)
+    else:
+        ap.error("one of --kernels, --stats, --ab")
+
+
+if __name__ == "__main__":
+    main()
