@@ -48,31 +48,75 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
     return s;
 }
 
+// The kernels below touch 64 KB at batch 4 (4x4 pixels, 512 channels): their time is the number of dependent memory round trips a
+// thread makes, not bytes.  Every loop therefore fetches all it needs for MBSTD_U elements (all G group members of each) before the
+// first use, at clamped addresses where an element or a group member does not exist, and the padded copies fetch the G images of a
+// position together instead of one image after the other.  The sums run in the order they always did (per thread over i ascending,
+// then block_sum_d), so every result is bit for bit what the one-load-at-a-time loops gave.
+#define MBSTD_U 8
+// the group's members g < G (G <= 4), unrolled: a loop to the runtime G would index the per-member register arrays dynamically (scratch)
+#define MBSTD_FOR_G(g) _Pragma("unroll") for (int g = 0; g < 4; ++g) if (g < G)
+// sqrt(var + eps) of the G values v (the group's standard deviation at one position and channel); mu is returned too
+__device__ __forceinline__ float mbstd_std(const float (&v)[4], int G, float& mu) {
+    mu = 0.f;
+    MBSTD_FOR_G(g) mu += v[g];
+    mu /= G;
+    float var = 0.f;
+    MBSTD_FOR_G(g) { const float d = v[g] - mu; var += d * d; }
+    return sqrtf(var / G + 1e-8f);
+}
+// sum over the slot's G images and HW positions of the statistic channel of dy (per thread, before block_sum_d)
+template <typename T>
+__device__ __forceinline__ double mbstd_gy_partial(const T* __restrict__ dy, int G, int M, int m, int HW, int C, int Cpad) {
+    double acc = 0.0;
+    for (int i0 = threadIdx.x; i0 < G * HW; i0 += MBSTD_U * blockDim.x) {
+        float t[MBSTD_U];
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u) {
+            const int i = i0 + u * blockDim.x, ii = i < G * HW ? i : G * HW - 1, g = ii / HW, p = ii % HW;
+            t[u] = to_f(dy[((size_t)(g * M + m) * HW + p) * Cpad + C]);
+        }
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u)
+            if (i0 + u * (int)blockDim.x < G * HW) acc += (double)t[u];
+    }
+    return acc;
+}
+// y[b][p][0..Cpad) = (src[b][p][0..C), stat, 0...) for the slot's G images: this block's share of the positions
+template <typename T>
+__device__ __forceinline__ void mbstd_padded_copy(const T* __restrict__ src, T* __restrict__ y, float stat, int G, int M, int m, int HW,
+                                                  int C, int Cpad) {
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < HW * Cpad; i += gridDim.y * blockDim.x) {
+        const int p = i / Cpad, c = i % Cpad, cc = c < C ? c : C - 1;
+        T v[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) v[g] = src[((size_t)((g < G ? g : 0) * M + m) * HW + p) * C + cc];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (g < G) y[((size_t)(g * M + m) * HW + p) * Cpad + c] = c < C ? from_f<T>(to_f(v[g])) : from_f<T>(c == C ? stat : 0.f);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(1024) void mbstd_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int HW, int C, int Cpad) {
     __shared__ double sh[16];
     const int G = B < 4 ? B : 4, M = B / G, m = blockIdx.x, n = HW * C;
     double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        float v[4], mu = 0.f;
-        for (int g = 0; g < G; ++g) { v[g] = to_f(x[(size_t)(g * M + m) * n + i]); mu += v[g]; }
-        mu /= G;
-        float var = 0.f;
-        for (int g = 0; g < G; ++g) { const float d = v[g] - mu; var += d * d; }
-        acc += (double)sqrtf(var / G + 1e-8f);
+    for (int i0 = threadIdx.x; i0 < n; i0 += MBSTD_U * blockDim.x) {
+        float v[MBSTD_U][4];
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u) {
+            const int i = i0 + u * blockDim.x, ii = i < n ? i : n - 1;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) v[u][g] = to_f(x[(size_t)((g < G ? g : 0) * M + m) * n + ii]);
+        }
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u)
+            if (i0 + u * (int)blockDim.x < n) { float mu; acc += (double)mbstd_std(v[u], G, mu); }
     }
     const float stat = (float)(block_sum_d(acc, sh) / n);
     // every block of the slot computed the statistic (redundantly: it is a 32-KB reduction); the padded copy is split over them
-    for (int g = 0; g < G; ++g) {
-        const size_t b = (size_t)(g * M + m);
-        for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < HW * Cpad; i += gridDim.y * blockDim.x) {
-            const int p = i / Cpad, c = i % Cpad;
-            float v = 0.f;
-            if (c < C) v = to_f(x[(b * HW + p) * C + c]);
-            else if (c == C) v = stat;
-            y[(b * HW + p) * Cpad + c] = from_f<T>(v);
-        }
-    }
+    mbstd_padded_copy(x, y, stat, G, M, m, HW, C, Cpad);
 }
 
 template <typename T>
@@ -80,24 +124,21 @@ __global__ __launch_bounds__(1024) void mbstd_bwd_kernel(const T* __restrict__ d
                                                         int HW, int C, int Cpad) {
     __shared__ double sh[16];
     const int G = B < 4 ? B : 4, M = B / G, m = blockIdx.x, n = HW * C;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < G * HW; i += blockDim.x) {
-        const int g = i / HW, p = i % HW;
-        acc += (double)to_f(dy[((size_t)(g * M + m) * HW + p) * Cpad + C]);
-    }
+    const double acc = mbstd_gy_partial(dy, G, M, m, HW, C, Cpad);
     const float k = (float)(block_sum_d(acc, sh) / n) / G;              // gy / (C*HW*G)
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         const int p = i / C, c = i % C;
-        float v[4], mu = 0.f;
-        for (int g = 0; g < G; ++g) { v[g] = to_f(x[(size_t)(g * M + m) * n + i]); mu += v[g]; }
-        mu /= G;
-        float var = 0.f;
-        for (int g = 0; g < G; ++g) { const float d = v[g] - mu; var += d * d; }
-        const float s = sqrtf(var / G + 1e-8f);
-        for (int g = 0; g < G; ++g) {
-            const size_t b = (size_t)(g * M + m);
-            dx[b * n + i] = from_f<T>(to_f(dy[(b * HW + p) * Cpad + c]) + k * (v[g] - mu) / s);
+        float v[4], d[4], mu;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const size_t b = (size_t)((g < G ? g : 0) * M + m);
+            v[g] = to_f(x[b * n + i]);
+            d[g] = to_f(dy[(b * HW + p) * Cpad + c]);
         }
+        const float s = mbstd_std(v, G, mu);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (g < G) dx[(size_t)(g * M + m) * n + i] = from_f<T>(d[g] + k * (v[g] - mu) / s);
     }
 }
 
@@ -106,50 +147,54 @@ __global__ __launch_bounds__(1024) void mbstd_bwd2_kernel(const T* __restrict__ 
                                                          T* __restrict__ ddy, T* __restrict__ gx, int B, int HW, int C, int Cpad) {
     __shared__ double sh[16];
     const int G = B < 4 ? B : 4, M = B / G, m = blockIdx.x, n = HW * C;
-    double a_gy = 0.0, a_dd = 0.0;
-    for (int i = threadIdx.x; i < G * HW; i += blockDim.x) {
-        const int g = i / HW, p = i % HW;
-        a_gy += (double)to_f(dy[((size_t)(g * M + m) * HW + p) * Cpad + C]);
-    }
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        float v[4], mu = 0.f;
-        for (int g = 0; g < G; ++g) { v[g] = to_f(x[(size_t)(g * M + m) * n + i]); mu += v[g]; }
-        mu /= G;
-        float var = 0.f, dot = 0.f;
-        for (int g = 0; g < G; ++g) {
-            const float d = v[g] - mu;
-            var += d * d;
-            dot += d * to_f(ggx[(size_t)(g * M + m) * n + i]);
+    const double a_gy = mbstd_gy_partial(dy, G, M, m, HW, C, Cpad);
+    double a_dd = 0.0;
+    for (int i0 = threadIdx.x; i0 < n; i0 += MBSTD_U * blockDim.x) {
+        float v[MBSTD_U][4], gg[MBSTD_U][4];
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u) {
+            const int i = i0 + u * blockDim.x, ii = i < n ? i : n - 1;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const size_t o = (size_t)((g < G ? g : 0) * M + m) * n + ii;
+                v[u][g] = to_f(x[o]); gg[u][g] = to_f(ggx[o]);
+            }
         }
-        a_dd += (double)(dot / sqrtf(var / G + 1e-8f));
+#pragma unroll
+        for (int u = 0; u < MBSTD_U; ++u)
+            if (i0 + u * (int)blockDim.x < n) {
+                float mu = 0.f;
+                MBSTD_FOR_G(g) mu += v[u][g];
+                mu /= G;
+                float var = 0.f, dot = 0.f;
+                MBSTD_FOR_G(g) {
+                    const float d = v[u][g] - mu;
+                    var += d * d;
+                    dot += d * gg[u][g];
+                }
+                a_dd += (double)(dot / sqrtf(var / G + 1e-8f));
+            }
     }
     const float k = (float)(block_sum_d(a_gy, sh) / n) / G;             // gy / (C*HW*G)
     const float dstat = (float)(block_sum_d(a_dd, sh) / n) / G;         // d L / d gy[m]
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         float v[4], gg[4], mu = 0.f;
-        for (int g = 0; g < G; ++g) {
-            v[g] = to_f(x[(size_t)(g * M + m) * n + i]); mu += v[g];
-            gg[g] = to_f(ggx[(size_t)(g * M + m) * n + i]);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const size_t o = (size_t)((g < G ? g : 0) * M + m) * n + i;
+            v[g] = to_f(x[o]); gg[g] = to_f(ggx[o]);
         }
+        MBSTD_FOR_G(g) mu += v[g];
         mu /= G;
         float var = 0.f, dot = 0.f;
-        for (int g = 0; g < G; ++g) { const float d = v[g] - mu; var += d * d; dot += d * gg[g]; }
+        MBSTD_FOR_G(g) { const float d = v[g] - mu; var += d * d; dot += d * gg[g]; }
         const float s = sqrtf(var / G + 1e-8f);
         float u[4], um = 0.f;
-        for (int g = 0; g < G; ++g) { u[g] = gg[g] / s - dot * (v[g] - mu) / (G * s * s * s); um += u[g]; }
+        MBSTD_FOR_G(g) { u[g] = gg[g] / s - dot * (v[g] - mu) / (G * s * s * s); um += u[g]; }
         um /= G;
-        for (int g = 0; g < G; ++g) gx[(size_t)(g * M + m) * n + i] = from_f<T>(k * (u[g] - um));
+        MBSTD_FOR_G(g) gx[(size_t)(g * M + m) * n + i] = from_f<T>(k * (u[g] - um));
     }
-    for (int g = 0; g < G; ++g) {
-        const size_t b = (size_t)(g * M + m);
-        for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < HW * Cpad; i += gridDim.y * blockDim.x) {
-            const int p = i / Cpad, c = i % Cpad;
-            float v = 0.f;
-            if (c < C) v = to_f(ggx[(b * HW + p) * C + c]);
-            else if (c == C) v = dstat;
-            ddy[(b * HW + p) * Cpad + c] = from_f<T>(v);
-        }
-    }
+    mbstd_padded_copy(ggx, ddy, dstat, G, M, m, HW, C, Cpad);
 }
 
 #ifndef MBSTD_NB
@@ -196,12 +241,80 @@ extern "C" int sgx_mbstd_bwd2(const void* ggx, const void* dy, const void* x, vo
 //   colsum : colsum[row of C] = cscale * sum_k A'[row][k]      -- with A = gy^T this is the bias gradient, out of the
 //            same launch as the weight gradient (written by the blocks of column tile 0)
 struct GemmFuse { const float* amask; const float* bias; float bscale; int act; float* colsum; float cscale; };
+// One 16-k step of a lane: its four operand values a4 (row ic of op(A), k = kk..kk+3) and b4 (column jc of op(B)).  No branch depends
+// on the lane: rows / columns beyond the matrix are read at the clamped index ic / jc (their products land in output rows / columns
+// that are never stored), and in the K tail (TAIL) a k beyond ke is read at ke - 1 and replaced by zero.  That lets the compiler issue
+// the loads of several steps back to back; with a branch per element every load waited for the one before it (8 - 17 dependent
+// round trips per wave at K = 512: the t00 shapes took 13.5 us, the K = 4 outer product 20.7).
+template <bool VA, bool VB, bool MASK, bool TAIL>
+__device__ __forceinline__ void gemm_step_load(const float* __restrict__ A, const float* __restrict__ am, const float* __restrict__ Bm,
+                                               size_t arow, size_t sa_k, size_t bcol, size_t sb_k, int kk, int ke, float (&a4)[4],
+                                               float (&b4)[4]) {
+    if (VA && !TAIL) {
+        const float4 t = *reinterpret_cast<const float4*>(A + arow + kk);
+        a4[0] = t.x; a4[1] = t.y; a4[2] = t.z; a4[3] = t.w;
+        if (MASK) {
+            const float4 m = *reinterpret_cast<const float4*>(am + arow + kk);
+            a4[0] *= lrelu_slope(m.x); a4[1] *= lrelu_slope(m.y); a4[2] *= lrelu_slope(m.z); a4[3] *= lrelu_slope(m.w);
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int kc = (TAIL && kk + s >= ke) ? ke - 1 : kk + s;
+            const size_t o = arow + kc * sa_k;
+            float v = A[o];
+            if (MASK) v *= lrelu_slope(am[o]);
+            a4[s] = (TAIL && kk + s >= ke) ? 0.f : v;
+        }
+    }
+    if (VB && !TAIL) {
+        const float4 t = *reinterpret_cast<const float4*>(Bm + bcol + kk);
+        b4[0] = t.x; b4[1] = t.y; b4[2] = t.z; b4[3] = t.w;
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int kc = (TAIL && kk + s >= ke) ? ke - 1 : kk + s;
+            const float v = Bm[kc * sb_k + bcol];
+            b4[s] = (TAIL && kk + s >= ke) ? 0.f : v;
+        }
+    }
+}
+// U = 16-k steps whose loads are in flight together
+template <int U, bool VA, bool VB, bool MASK>
+__device__ __forceinline__ f32x4 gemm_wave_slice(const float* __restrict__ A, const float* __restrict__ am, const float* __restrict__ Bm,
+                                                 size_t arow, size_t sa_k, size_t bcol, size_t sb_k, int kb, int ke, int q) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int k = kb;
+    for (; k + 16 * U <= ke; k += 16 * U) {
+        float a[U][4], b[U][4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) gemm_step_load<VA, VB, MASK, false>(A, am, Bm, arow, sa_k, bcol, sb_k, k + 16 * u + 4 * q, ke, a[u], b[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], b[u][s], acc, 0, 0, 0);
+    }
+    for (; k + 16 <= ke; k += 16) {
+        float a[4], b[4];
+        gemm_step_load<VA, VB, MASK, false>(A, am, Bm, arow, sa_k, bcol, sb_k, k + 4 * q, ke, a, b);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+    }
+    if (k < ke) {                                              // K tail of the slice: fewer than 16 k left
+        float a[4], b[4];
+        gemm_step_load<VA, VB, MASK, true>(A, am, Bm, arow, sa_k, bcol, sb_k, k + 4 * q, ke, a, b);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+    }
+    return acc;
+}
+template <int U>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ Bm, float* __restrict__ Cm,
                                                        int M, int N, int K, int ta, int tb, float alpha, GemmFuse fu) {
     __shared__ float red[4][16][17];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, l15 = lane & 15;
     const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
-    const int i = i0 + l15, j = j0 + l15;
+    const int ic = i0 + l15 < M ? i0 + l15 : M - 1, jc = j0 + l15 < N ? j0 + l15 : N - 1;
     // split K: blockIdx.z owns [z*kz, (z+1)*kz) (partials go to Cm + z*M*N, summed by gemm_splitk_reduce), its 4 waves
     // split that range again
     const int kz = ((K + (int)gridDim.z - 1) / (int)gridDim.z + 15) / 16 * 16;
@@ -209,46 +322,22 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     const int kper = (((kz1 > kz0 ? kz1 - kz0 : 0) + 3) / 4 + 15) / 16 * 16;   // K slice per wave, multiple of 16
     const int kb = kz0 + wave * kper, ke = (kb + kper < kz1) ? kb + kper : kz1;
     Cm += (size_t)blockIdx.z * M * N;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const size_t sa_i = ta ? 1 : (size_t)K, sa_k = ta ? (size_t)M : 1;
     const size_t sb_k = tb ? 1 : (size_t)N, sb_j = tb ? (size_t)K : 1;
-    // 16 k per iteration: lane group q owns k = k0+4q..+3 (any k order is valid as long as A and B agree), so an
+    const size_t arow = ic * sa_i, bcol = jc * sb_j;
+    // 16 k per step: lane group q owns k = k0+4q..+3 (any k order is valid as long as A and B agree), so an
     // operand whose k axis is contiguous is fetched with one 16-byte load per lane instead of four 4-byte ones.
     const bool va = !ta && (K % 4 == 0), vb = tb && (K % 4 == 0);
-#pragma unroll 8
-    for (int k = kb; k < ke; k += 16) {
-        const int kk = k + 4 * q;
-        float a4[4] = {0.f, 0.f, 0.f, 0.f}, b4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (i < M) {
-            if (va && kk + 3 < ke) {
-                const float4 t = *reinterpret_cast<const float4*>(A + i * sa_i + kk);
-                a4[0] = t.x; a4[1] = t.y; a4[2] = t.z; a4[3] = t.w;
-                if (fu.amask) {
-                    const float4 m = *reinterpret_cast<const float4*>(fu.amask + i * sa_i + kk);
-                    a4[0] *= lrelu_slope(m.x); a4[1] *= lrelu_slope(m.y); a4[2] *= lrelu_slope(m.z); a4[3] *= lrelu_slope(m.w);
-                }
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    if (kk + s < ke) {
-                        const size_t o = i * sa_i + (kk + s) * sa_k;
-                        a4[s] = A[o];
-                        if (fu.amask) a4[s] *= lrelu_slope(fu.amask[o]);
-                    }
-            }
-        }
-        if (j < N) {
-            if (vb && kk + 3 < ke) {
-                const float4 t = *reinterpret_cast<const float4*>(Bm + j * sb_j + kk);
-                b4[0] = t.x; b4[1] = t.y; b4[2] = t.z; b4[3] = t.w;
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) if (kk + s < ke) b4[s] = Bm[(kk + s) * sb_k + j * sb_j];
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s], b4[s], acc, 0, 0, 0);
+    f32x4 acc;
+#define GEMM_SLICE(VA, VB, MK) acc = gemm_wave_slice<U, VA, VB, MK>(A, fu.amask, Bm, arow, sa_k, bcol, sb_k, kb, ke, q)
+    if (fu.amask) {
+        if (va) { if (vb) GEMM_SLICE(true, true, true); else GEMM_SLICE(true, false, true); }
+        else    { if (vb) GEMM_SLICE(false, true, true); else GEMM_SLICE(false, false, true); }
+    } else {
+        if (va) { if (vb) GEMM_SLICE(true, true, false); else GEMM_SLICE(true, false, false); }
+        else    { if (vb) GEMM_SLICE(false, true, false); else GEMM_SLICE(false, false, false); }
     }
+#undef GEMM_SLICE
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wave][q * 4 + r][l15] = acc[r];
     __syncthreads();
@@ -263,12 +352,51 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     if (fu.colsum && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 16 && i0 + (int)threadIdx.x < M) {
         const int row = i0 + threadIdx.x;                     // sum over the whole K axis of row `row` of op(A) (masked)
         float t = 0.f;
-        for (int k = 0; k < K; ++k) {
+        int k = 0;
+        for (; k + 8 <= K; k += 8) {                           // 8 (x2) loads in flight, summed in k order
+            float v[8], m[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const size_t o = row * sa_i + (k + u) * sa_k;
+                v[u] = A[o];
+                m[u] = fu.amask ? fu.amask[o] : 1.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t += fu.amask ? v[u] * lrelu_slope(m[u]) : v[u];
+        }
+        for (; k < K; ++k) {
             const size_t o = row * sa_i + k * sa_k;
             t += fu.amask ? A[o] * lrelu_slope(fu.amask[o]) : A[o];
         }
         fu.colsum[row] = fu.cscale * t;
     }
+}
+// K <= 4 with B row-major (tb = 0) is an outer product, not a GEMM: C = alpha * sum_k A[:, k] B[k, :] is M * N stores and next to
+// no reads (batch 4: dW[512][8192] = gy^T x of the discriminator's dense layer, 16 MB written from 130 KB).  A 16x16 tile per block
+// makes that 16384 four-wave blocks of one MFMA step, an LDS round trip and 4-byte stores (20.7 us); here a lane owns four
+// consecutive columns and makes one 16-byte store.  The sum is formed the way the MFMA forms it for these shapes, a chain of fused
+// multiply-adds in k order from zero, so the result is bit for bit the tile kernel's (tools/small_probe.py compares the two builds).
+__global__ __launch_bounds__(256) void gemm_outer_kernel(const float* __restrict__ A, const float* __restrict__ Bm, float* __restrict__ Cm,
+                                                         int M, int N, int K, size_t sa_i, size_t sa_k, float alpha) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, n4 = (size_t)N / 4;
+    if (idx >= (size_t)M * n4) return;
+    const size_t i = idx / n4, j = (idx % n4) * 4;
+    float a[4];
+    float4 b[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int kc = k < K ? k : 0;
+        a[k] = A[i * sa_i + kc * sa_k];
+        b[k] = *reinterpret_cast<const float4*>(Bm + (size_t)kc * N + j);
+    }
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < K) {
+            acc.x = fmaf(a[k], b[k].x, acc.x); acc.y = fmaf(a[k], b[k].y, acc.y); acc.z = fmaf(a[k], b[k].z, acc.z); acc.w = fmaf(a[k], b[k].w, acc.w);
+        }
+    acc.x *= alpha; acc.y *= alpha; acc.z *= alpha; acc.w *= alpha;
+    *reinterpret_cast<float4*>(Cm + i * N + j) = acc;
 }
 __global__ void gemm_splitk_reduce(const float* __restrict__ part, float* __restrict__ Cm, int MN, int splits, float alpha) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -297,12 +425,25 @@ static int gemm_launch(const float* A, const float* Bm, float* C, int M, int N, 
     if (splits > 1 && (!ws || ws_bytes < (size_t)splits * M * N * sizeof(float) || fu.bias || fu.act || fu.colsum)) splits = 1;
     SGX_NOTE(2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N), "gemm %dx%dx%d t%d%d%s", M, N, K, ta, tb,
              fu.amask || fu.bias || fu.colsum ? " fused" : "");
+    const bool fused = fu.amask || fu.bias || fu.act || fu.colsum;
+    if (K <= 4 && !tb && N % 4 == 0 && !fused && ((uintptr_t)Bm | (uintptr_t)C) % 16 == 0) {
+        const size_t n = (size_t)M * (N / 4);
+        hipLaunchKernelGGL(gemm_outer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, Bm, C, M, N, K, ta ? (size_t)1 : (size_t)K,
+                           ta ? (size_t)M : (size_t)1, alpha);
+        SGX_LAUNCH_CHECK("gemm_outer");
+        return 0;
+    }
+    // A wave's K slice of 128 or more (K = 512 unsplit, every split-K launch) runs with the loads of 8 steps in flight: 106 registers.
+    // Shorter slices never enter that loop, and their launches are many small blocks (K = 8: 1024 of them) that want the
+    // 8 blocks per CU a small register file allows, so they get the instantiation without the unrolled loop.
+    const int ksplit = (K + splits - 1) / splits;
+    auto kern = ksplit >= 512 ? gemm_f32_kernel<8> : gemm_f32_kernel<1>;
     if (splits == 1) {
-        hipLaunchKernelGGL(gemm_f32_kernel, dim3((N + 15) / 16, (M + 15) / 16, 1), dim3(256), 0, st, A, Bm, C, M, N, K, ta, tb, alpha, fu);
+        hipLaunchKernelGGL(kern, dim3((N + 15) / 16, (M + 15) / 16, 1), dim3(256), 0, st, A, Bm, C, M, N, K, ta, tb, alpha, fu);
         SGX_LAUNCH_CHECK("gemm_f32");
         return 0;
     }
-    hipLaunchKernelGGL(gemm_f32_kernel, dim3((N + 15) / 16, (M + 15) / 16, splits), dim3(256), 0, st, A, Bm, (float*)ws, M, N, K, ta, tb, 1.0f, fu);
+    hipLaunchKernelGGL(kern, dim3((N + 15) / 16, (M + 15) / 16, splits), dim3(256), 0, st, A, Bm, (float*)ws, M, N, K, ta, tb, 1.0f, fu);
     SGX_LAUNCH_CHECK("gemm_f32");
     hipLaunchKernelGGL(gemm_splitk_reduce, dim3((M * N + 255) / 256), dim3(256), 0, st, (const float*)ws, C, M * N, splits, alpha);
     SGX_LAUNCH_CHECK("gemm_splitk_reduce");
@@ -338,7 +479,14 @@ extern "C" int sgx_linear_bwd_param(const float* gy, const float* y_act, const f
 // work: one launch forward, two backward.  tab: G rows of SGX_STYLE_ROW 64-bit words
 //   [W, bias, N, y offset (elements, = B * sum of earlier N), first tile, w_mul bits, b_mul bits, layer]
 #define STYLE_MAXB 32
+// group of a tile: the last row whose first tile is <= tile.  Lane g reads row g's first tile and one ballot counts the rows that
+// qualify (first tiles ascend), where a walk over the rows made up to G dependent reads before the block's first weight load.
 __device__ __forceinline__ int style_group(const long long* __restrict__ tab, int G, unsigned tile) {
+    if (G <= 64) {
+        const int l = threadIdx.x & 63;
+        const bool le = l < G && (unsigned)tab[(l < G ? l : 0) * SGX_STYLE_ROW + 4] <= tile;
+        return __builtin_amdgcn_readfirstlane(__popcll(__ballot(le)) - 1);
+    }
     int g = 0;
     while (g + 1 < G && (unsigned)tab[(g + 1) * SGX_STYLE_ROW + 4] <= tile) ++g;
     return g;
@@ -355,23 +503,39 @@ __global__ __launch_bounds__(256) void style_fwd_kernel(const float* __restrict_
     const int N = (int)r[2], layer = (int)r[7];
     const float w_mul = __uint_as_float((unsigned)r[5]), b_mul = __uint_as_float((unsigned)r[6]);
     const float* x = lm + (size_t)layer * B * D;
-    for (int i = threadIdx.x; i < B * D / 4; i += 256) reinterpret_cast<float4*>(xs)[i] = reinterpret_cast<const float4*>(x)[i];
-    __syncthreads();
     const int col = threadIdx.x >> 4, kl = threadIdx.x & 15;
     const int n = ((int)blockIdx.x - (int)r[4]) * 16 + col;
+    // A lane's share of weight row n is D / 64 16-byte pieces (8 at D = 512).  STYLE_U of them are requested before the first is
+    // used -- the first STYLE_U before x is staged, so the weight stream starts with the block -- and consumed in k order: the
+    // sums are the ones the one-load-per-iteration loop formed (that loop was D / 64 dependent round trips to memory: 19 us).
+    constexpr int STYLE_U = 8;
+    const float* wrow = W + (size_t)(n < N ? n : N - 1) * D;
+    float4 w[STYLE_U];
+#pragma unroll
+    for (int u = 0; u < STYLE_U; ++u) { const int k = kl * 4 + 64 * u; w[u] = *reinterpret_cast<const float4*>(wrow + (k < D ? k : D - 4)); }
+    for (int i = threadIdx.x; i < B * D / 4; i += 256) reinterpret_cast<float4*>(xs)[i] = reinterpret_cast<const float4*>(x)[i];
+    __syncthreads();
     float acc[MB];
 #pragma unroll
     for (int b = 0; b < MB; ++b) acc[b] = 0.f;
-    if (n < N)
-        for (int k = kl * 4; k < D; k += 64) {
-            const float4 w = *reinterpret_cast<const float4*>(W + (size_t)n * D + k);
+    for (int k0 = kl * 4; k0 < D; k0 += 64 * STYLE_U) {
+        if (k0 != kl * 4) {
 #pragma unroll
-            for (int b = 0; b < MB; ++b)
-                if (b < B) {
-                    const float4 v = *reinterpret_cast<const float4*>(xs + b * D + k);
-                    acc[b] += (w.x * v.x + w.y * v.y) + (w.z * v.z + w.w * v.w);
-                }
+            for (int u = 0; u < STYLE_U; ++u) { const int k = k0 + 64 * u; w[u] = *reinterpret_cast<const float4*>(wrow + (k < D ? k : D - 4)); }
         }
+#pragma unroll
+        for (int u = 0; u < STYLE_U; ++u) {
+            const int k = k0 + 64 * u;
+            if (k < D) {
+#pragma unroll
+                for (int b = 0; b < MB; ++b)
+                    if (b < B) {
+                        const float4 v = *reinterpret_cast<const float4*>(xs + b * D + k);
+                        acc[b] += (w[u].x * v.x + w[u].y * v.y) + (w[u].z * v.z + w[u].w * v.w);
+                    }
+            }
+        }
+    }
 #pragma unroll
     for (int b = 0; b < MB; ++b)
         if (b < B) {
@@ -409,21 +573,40 @@ __global__ __launch_bounds__(256) void style_bwd_data_kernel(const float* __rest
 #pragma unroll
     for (int b = 0; b < MB; ++b) acc[b] = 0.f;
     if (kk < D) {
-        // 16 independent weight loads in flight per lane, then the FMAs (a dependent one-load-per-iteration loop is pure latency)
+        // 16 independent weight loads per lane and chunk (a dependent one-load-per-iteration loop is pure latency), and the next
+        // chunk's 16 are requested before the FMAs of this one: a wave walks up to N / 4 = 256 rows, and with one chunk in flight at
+        // a time that was 16 round trips to memory in a row (34.5 us for 20 MB of weights at batch 4).  n order, hence every sum,
+        // is unchanged.
         int n = wave;
-        for (; n + 4 * 15 < N; n += 4 * 16) {
-            float w[16];
+        const int full = N > wave ? (N - wave + 3) / 4 / 16 : 0;   // chunks of 16 rows (stride 4) this wave owns entirely
+        float wa[16], wb[16];
+        auto ld = [&](float (&w)[16], int n0) {
 #pragma unroll
-            for (int u = 0; u < 16; ++u) w[u] = W[(size_t)(n + 4 * u) * D + kk];
+            for (int u = 0; u < 16; ++u) w[u] = W[(size_t)(n0 + 4 * u) * D + kk];
+        };
+        auto fm = [&](const float (&w)[16], int n0) {
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                const float4* row = reinterpret_cast<const float4*>(sh + (size_t)(n + 4 * u) * MB);
+                const float4* row = reinterpret_cast<const float4*>(sh + (size_t)(n0 + 4 * u) * MB);
 #pragma unroll
                 for (int q = 0; q < MB / 4; ++q) {
                     const float4 g4 = row[q];
                     acc[4 * q] += g4.x * w[u]; acc[4 * q + 1] += g4.y * w[u]; acc[4 * q + 2] += g4.z * w[u]; acc[4 * q + 3] += g4.w * w[u];
                 }
             }
+        };
+        if constexpr (MB <= 8) {
+            int c = 0;
+            if (full > 0) ld(wa, n);
+            for (; c + 1 < full; c += 2, n += 128) {
+                ld(wb, n + 64);
+                fm(wa, n);
+                if (c + 2 < full) ld(wa, n + 128);
+                fm(wb, n + 64);
+            }
+            if (c < full) { fm(wa, n); n += 64; }
+        } else {                                               // MB accumulators + two chunks do not fit the register file: one chunk at a time
+            for (int c = 0; c < full; ++c, n += 64) { ld(wa, n); fm(wa, n); }
         }
         for (; n < N; n += 4) {
             const float w = W[(size_t)n * D + kk];
