@@ -1089,7 +1089,7 @@ extern "C" int sgx_up2_add(const void* x, const void* a, void* y, int B, int H, 
     const double es = dtype == SGX_F32 ? 4.0 : 2.0;
     SGX_NOTE(0.0, 9.0 * es * B * H * W * C, "up2+add B%d %dx%d C%d", B, H, W, C);
     const size_t nout = (size_t)B * H * W * 4 * C;
-    if (dtype == SGX_F32 && C == 3 && (2 * W * 3) % 4 == 0)
+    if (dtype == SGX_F32 && C == 3 && (2 * W * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
         hipLaunchKernelGGL(up2_add_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (const float*)a, (float*)y, B, H, W, scale);
     else if (dtype == SGX_F32)
         hipLaunchKernelGGL(up2_add_kernel<float>, dim3(grid_for(nout)), dim3(256), 0, st, (const float*)x, (const float*)a, (float*)y, B, H, W, C, scale);
@@ -1106,7 +1106,8 @@ extern "C" int sgx_up2(const void* x, void* y, int B, int H, int W, int C, float
         if (C % 4 == 0) hipLaunchKernelGGL((up2_kernel<float, true>), dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
         else if (C == 3 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
             hipLaunchKernelGGL(up2_rgb4_kernel, dim3(grid_all((size_t)B * H * (W / 4))), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
-        else if (C == 3 && (2 * W * 3) % 4 == 0) hipLaunchKernelGGL(up2_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
+        else if (C == 3 && (2 * W * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)           // (16-byte stores: y aligned; x is read by the float)
+            hipLaunchKernelGGL(up2_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
         else hipLaunchKernelGGL((up2_kernel<float, false>), dim3(grid_for(nout)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
     } else {
         if (C % 8 == 0) hipLaunchKernelGGL((up2_kernel<bf16_t, true>), dim3(grid_all(nout / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C, scale);
