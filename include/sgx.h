@@ -250,6 +250,24 @@ int sgx_downsample_fade_rgb(const float* x, float* out, int B, int H, int W, flo
 size_t sgx_diffaug_ws_bytes(int B, int H, int W);
 int sgx_diffaug(const float* x, float* y, const float* u, int B, int H, int W, int policy_bits, int adjoint, int with_bias, void* ws,
                 size_t ws_bytes, void* stream);
+/* Adaptive discriminator augmentation (Karras et al., NeurIPS 2020) on the DiffAugment kernels: every op is applied to an image with
+ * probability p, and p is steered on the device from r_t = E[sign(D(real))] towards a target.
+ *   state: DEVICE fp32 [8] = { p, sum of signs, images counted, calls since the last update, last r_t, updates made, 0, 0 }.
+ * sgx_ada_gates: gu DEVICE fp32 [B][3] uniforms in [0,1);  img_bits[b] (int32 [B]) = policy_bits & (1 [gu[b][0] < p] | 2 [gu[b][1] < p] |
+ *   4 [gu[b][2] < p]) with p = state[0] read on the device and strict < in fp32: p = 0 gates nothing, p = 1 everything.  The bits are
+ *   made once per D evaluation; every later pass of that evaluation (adjoint, linear part, R1 double backward) reads them, never p.
+ * sgx_diffaug_gated: sgx_diffaug with image b transformed under (policy_bits & img_bits[b]) instead of one policy for the batch;
+ *   policy_bits (the union) only decides whether the sum pass is launched; workspace as for sgx_diffaug.  An image whose bits are 0 is
+ *   copied bit-exactly (forward and adjoint); an image without the colour bit does no arithmetic on its values (gathers and zeros).
+ * sgx_ada_update: one block.  S = sum over b of sign(real_logits[b]) (+1 / -1; 0 for +-0 and NaN), summed as an integer and converted
+ *   to fp32.  With every product and sum rounded to fp32 on its own:  state[1] += S;  state[2] += B;  state[3] += 1;  and when state[3]
+ *   >= interval:  r_t = state[1] / state[2];  p = min(max(p + sign(r_t - target) * (adjust_per_image * state[2]), 0), 1) (the sign by
+ *   comparing r_t with target: 0 when equal);  state[4] = r_t;  state[5] += 1;  state[1..3] = 0.  adjust_per_image = 1 / (ada_kimg *
+ *   1000) as computed by the caller.  B <= 2^24.  Replaces the augment pipe's p buffer and the training loop's host-side heuristic. */
+int sgx_ada_gates(const float* gu, const float* state, int policy_bits, int* img_bits, int B, void* stream);
+int sgx_diffaug_gated(const float* x, float* y, const float* u, const int* img_bits, int B, int H, int W, int policy_bits, int adjoint,
+                      int with_bias, void* ws, size_t ws_bytes, void* stream);
+int sgx_ada_update(const float* real_logits, int B, float* state, float target, float adjust_per_image, int interval, void* stream);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

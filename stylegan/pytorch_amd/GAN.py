@@ -346,12 +346,35 @@ class Discriminator(nn.Module):
 
     def __init__(self, resolution, num_channels=3, conditional=False, n_classes=0, fmap_base=8192, fmap_decay=1.0,
                  fmap_max=512, nonlinearity='lrelu', use_wscale=True, mbstd_group_size=4, mbstd_num_features=1,
-                 blur_filter=None, structure='linear', act_dtype=torch.float32, diffaug_policy="", **kwargs):
+                 blur_filter=None, structure='linear', act_dtype=torch.float32, diffaug_policy="", ada_target=0.0, ada_interval=4,
+                 ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
         # 'color,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
+        # ADA (Karras et al., NeurIPS 2020) on top of the policy: each op with probability p, p steered on the device towards
+        # E[sign(D(real))] == ada_target (0: off -- no buffer, the policy applies always, exactly the code path without these keys)
+        self.ada_target, self.ada_interval = float(ada_target), int(ada_interval)
+        self.ada_kimg, self.ada_p_init = float(ada_kimg), float(ada_p_init)
+        if not 0.0 <= self.ada_target < 1.0:
+            raise ValueError(f"ada_target must be 0 (off) or in (0, 1), got {ada_target!r}")
+        if self.ada_interval != ada_interval or self.ada_interval < 1:
+            raise ValueError(f"ada_interval must be a positive integer, got {ada_interval!r}")
+        if not (self.ada_kimg > 0.0 and np.isfinite(self.ada_kimg)):
+            raise ValueError(f"ada_kimg must be positive, got {ada_kimg!r}")
+        if not 0.0 <= self.ada_p_init <= 1.0:
+            raise ValueError(f"ada_p_init must be in [0, 1], got {ada_p_init!r}")
+        self.ada = self.ada_target != 0.0
+        if self.ada:
+            if not self._diffaug_bits:
+                raise ValueError("ada_target needs a diffaug_policy: ADA gates the policy's ops, an empty policy has none")
+            # [p, sum of signs, images counted, calls since the last update, last r_t, updates made, 0, 0] (include/sgx.h); persistent,
+            # so a checkpoint resumes at its p
+            state = torch.zeros(8, dtype=torch.float32)
+            state[0] = self.ada_p_init
+            self.register_buffer("ada_state", state)
+            self._ada_adjust = 1.0 / (self.ada_kimg * 1000.0)            # p per image seen (passed to the controller as fp32)
         if conditional:
             # reference :326-330: the label embedding joins the image as num_channels extra channels of the from_rgb input
             assert n_classes > 0, "Conditional Discriminator requires n_class > 0"
@@ -394,11 +417,43 @@ class Discriminator(nn.Module):
     # (instead of fresh torch.rand draws)
     diffaug_override = None
 
+    # the same for ADA's gate uniforms: a [B,3] device tensor (op k of image b is on iff ada_gate_override[b, k] < p)
+    ada_gate_override = None
+    _ada_real = None                      # D(real) logits of the current dis_loss (detached), until ada_step consumes them
+
     def _diffaug(self, img):
         u = self.diffaug_override
-        if u is None:
-            u = torch.rand(img.shape[0], 7, device=img.device)           # torch's graph-safe generator: fresh draws at every replay
-        return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+        if not self.ada:
+            if u is None:
+                u = torch.rand(img.shape[0], 7, device=img.device)       # torch's graph-safe generator: fresh draws at every replay
+            return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+        # ADA: one draw per D evaluation, columns 0..6 the ops' parameters and 7..9 their gates.  The gates are turned into per-image
+        # bits ONCE, here; the adjoint, the linear part and the R1 double backward of this evaluation read the bits, never p.
+        gu = self.ada_gate_override
+        if u is None or gu is None:
+            r = torch.rand(img.shape[0], 10, device=img.device)
+            u = r[:, :7].contiguous() if u is None else u                 # (saved for the backward passes: contiguous once)
+            gu = r[:, 7:] if gu is None else gu
+        return F.call(F.DiffAugFn, img, u, self._diffaug_bits, F.ada_gates(gu, self.ada_state, self._diffaug_bits))
+
+    @property
+    def ada_p(self):
+        """Host copy of p (None with ADA off).  Waits for the GPU: for logs and tests, never on the step path."""
+        return float(self.ada_state[0]) if self.ada else None
+
+    def ada_observe(self, real_logits):
+        """Called by every ``dis_loss`` with its D(real) logits: keeps the detached tensor for ``ada_step`` (nothing is launched)."""
+        if self.ada and self.training:
+            self._ada_real = real_logits.detach()
+
+    def ada_step(self):
+        """One controller call with the D(real) logits the last ``dis_loss`` reported (``sgx_ada_update`` on the current stream; every
+        ``ada_interval`` calls p moves).  StyleGAN's D step calls this after ``dis_loss`` has returned -- D(fake), which may run on
+        another stream, has been joined by then, so no gate launch reads p while it is written; whoever drives the losses by hand
+        calls it at the same place.  Without a report since the last call (ADA off, eval mode) it does nothing."""
+        lg, self._ada_real = self._ada_real, None
+        if lg is not None:
+            F.ada_update(lg.float(), self.ada_state, self.ada_target, self._ada_adjust, self.ada_interval)
 
     def prepack(self, depth=None, img_shape=None):
         """Operand packs of every convolution whose weights changed since they were last packed (one launch), plus -- given the
@@ -521,6 +576,9 @@ class StyleGAN:
         self.dis = Discriminator(num_channels=num_channels, resolution=resolution, structure=self.structure,
                                  conditional=self.conditional, n_classes=self.n_classes, act_dtype=act_dtype,
                                  **d_args).to(self.device)
+        if self._ada_on() and self.dp is not None and self.dp.world_size > 1:
+            # r_t is a statistic of the GLOBAL batch: its two accumulators would need a cross-rank sum before every update
+            raise ValueError("ADA (model.dis.ada_target) is not supported with data parallelism over more than one rank")
         self.__setup_gen_optim(**g_opt_args)
         self.__setup_dis_optim(**d_opt_args)
         self.drift = drift
@@ -532,6 +590,9 @@ class StyleGAN:
         self._grad_buckets = {}                       # (kind, depth) -> dist.GradBuckets of that network's active parameters
         if self.dp is not None and self.gen.truncation is not None:
             self.gen._avg_latent_hook = lambda buf: self.dp.broadcast(buf, src=0)     # (after the deepcopy: the shadow has none)
+
+    def _ada_on(self):
+        return bool(getattr(self.dis, "ada", False))          # (a discriminator that is not this package's has no ADA)
 
     def __setup_gen_optim(self, learning_rate, beta_1, beta_2, eps):
         self.gen_optim = FusedAdam(self.gen.parameters(), lr=learning_rate, betas=(float(beta_1), float(beta_2)), eps=eps)
@@ -718,6 +779,10 @@ class StyleGAN:
             loss = self.loss.dis_loss(real_samples, make_fakes(), labels, depth, alpha)
         else:
             loss = self.loss.dis_loss(real_samples, make_fakes if lazy else make_fakes(), depth, alpha)
+        # ADA's controller, on the main stream and after dis_loss has returned: every gate launch of this step (D(real) here, D(fake)
+        # on the auxiliary stream, joined inside dis_loss) has read p before this write, and the backward reads the gates' bits only
+        if self._ada_on():
+            self.dis.ada_step()
         self._zero_grads("d", depth)
         side = self._param_stream(two_branches=aux is not None and lazy)
         self._sched_begin("d", depth, side)
@@ -856,7 +921,9 @@ class StyleGAN:
         key = (kind, int(depth), tuple(noise.shape), tuple(real_batch.shape), tuple(real_batch.stride()), real_batch.dtype,
                self.aux_stream, self.param_stream,                     # a captured graph bakes its stream structure in
                self.dis._diffaug_bits, self.dis.training,              # ... and whether (and from where) D's input is augmented
-               None if self.dis.diffaug_override is None else self.dis.diffaug_override.data_ptr())
+               None if self.dis.diffaug_override is None else self.dis.diffaug_override.data_ptr(),
+               (self.dis.ada_target, self.dis.ada_interval, self.dis.ada_kimg) if self._ada_on() else None,   # ... baked into the update launch
+               None if not self._ada_on() or self.dis.ada_gate_override is None else self.dis.ada_gate_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)
@@ -1061,8 +1128,12 @@ class StyleGAN:
                             probe = None
                     if self.is_feedback_batch(i, total_batches, feedback_factor):
                         elapsed = str(datetime.timedelta(seconds=time.time() - t_begin)).split('.')[0]
-                        logger.info("Elapsed: [%s] Step: %d  Batch: %d  D_Loss: %f  G_Loss: %f"
-                                    % (elapsed, step, i, dis_loss, gen_loss))
+                        ada = ""
+                        if self._ada_on():
+                            st = self.dis.ada_state.tolist()
+                            ada = "  ada_p=%.4f r_t=%.3f" % (st[0], st[4])
+                        logger.info("Elapsed: [%s] Step: %d  Batch: %d  D_Loss: %f  G_Loss: %f%s"
+                                    % (elapsed, step, i, dis_loss, gen_loss, ada))
                         os.makedirs(os.path.join(output, 'samples'), exist_ok=True)
                         gen_img_file = os.path.join(output, 'samples', "gen_" + str(current_depth) + "_" + str(epoch) + "_"
                                                     + str(i) + ".png")

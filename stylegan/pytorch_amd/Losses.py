@@ -10,6 +10,15 @@ import torch.nn.functional as TF
 from . import functional as F
 
 
+def _observe_real(dis, r_preds):
+    """Every ``dis_loss`` reports its D(real) logits once (no ``gen_loss`` does): with ADA on, the discriminator stashes the detached
+    tensor for the controller call that follows the loss (``Discriminator.ada_step``); otherwise nothing happens."""
+    observe = getattr(dis, "ada_observe", None)
+    if observe is not None:
+        observe(r_preds)
+    return r_preds
+
+
 class GANLoss:
     """Base class -- reference models/Losses.py:20-51.
 
@@ -46,7 +55,7 @@ class ConditionalGANLoss:
     _scaled = GANLoss._scaled
 
     def dis_loss(self, real_samps, fake_samps, labels, height, alpha):
-        r_preds = torch.squeeze(self.dis(real_samps, height, alpha, labels_in=labels))
+        r_preds = torch.squeeze(_observe_real(self.dis, self.dis(real_samps, height, alpha, labels_in=labels)))
         f_preds = torch.squeeze(self.dis(fake_samps, height, alpha, labels_in=labels))
         real_loss = TF.binary_cross_entropy_with_logits(r_preds, torch.ones_like(r_preds))
         fake_loss = TF.binary_cross_entropy_with_logits(f_preds, torch.zeros_like(f_preds))
@@ -64,7 +73,7 @@ class StandardGAN(GANLoss):
     predictions -- is what is computed here."""
 
     def dis_loss(self, real_samps, fake_samps, height, alpha):
-        r_preds = torch.squeeze(self.dis(real_samps, height, alpha))
+        r_preds = torch.squeeze(_observe_real(self.dis, self.dis(real_samps, height, alpha)))
         f_preds = torch.squeeze(self.dis(fake_samps, height, alpha))
         real_loss = TF.binary_cross_entropy_with_logits(r_preds, torch.ones_like(r_preds))
         fake_loss = TF.binary_cross_entropy_with_logits(f_preds, torch.zeros_like(f_preds))
@@ -79,7 +88,7 @@ class HingeGAN(GANLoss):
     """reference models/Losses.py:136-151."""
 
     def dis_loss(self, real_samps, fake_samps, height, alpha):
-        r_preds = self.dis(real_samps, height, alpha)
+        r_preds = _observe_real(self.dis, self.dis(real_samps, height, alpha))
         f_preds = self.dis(fake_samps, height, alpha)
         return self._scaled(torch.mean(TF.relu(1 - r_preds)) + torch.mean(TF.relu(1 + f_preds)))
 
@@ -92,7 +101,7 @@ class RelativisticAverageHingeGAN(GANLoss):
     ``batch_mean`` (the global mean under data parallelism, see GANLoss)."""
 
     def dis_loss(self, real_samps, fake_samps, height, alpha):
-        r_preds = self.dis(real_samps, height, alpha)
+        r_preds = _observe_real(self.dis, self.dis(real_samps, height, alpha))
         f_preds = self.dis(fake_samps, height, alpha)
         r_f_diff = r_preds - self.batch_mean(f_preds)
         f_r_diff = f_preds - self.batch_mean(r_preds)
@@ -149,6 +158,7 @@ class LogisticGAN(GANLoss):
         else:
             r_preds = self.dis(real_samps, height, alpha)
             r1 = None
+        _observe_real(self.dis, r_preds)
         if fake_logits is not None:
             f_preds = fake_logits()
         else:

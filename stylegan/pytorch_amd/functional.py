@@ -2306,7 +2306,7 @@ def diffaug_policy_bits(policy):
     return bits
 
 
-def _diffaug(x, u, bits, adjoint, with_bias):
+def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
     x, u = _c(x), _c(u)
     if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
         raise N.SgxError(f"diffaug: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
@@ -2319,54 +2319,94 @@ def _diffaug(x, u, bits, adjoint, with_bias):
     if bits & 1:
         nb = L.sgx_diffaug_ws_bytes(B, H, W)
         ws = N.workspace(nb, x.device)
-    N.check(L.sgx_diffaug(N.ptr(x), N.ptr(y), N.ptr(u), B, H, W, int(bits), int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream()),
-            "sgx_diffaug")
+    if img_bits is None:
+        N.check(L.sgx_diffaug(N.ptr(x), N.ptr(y), N.ptr(u), B, H, W, int(bits), int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream()),
+                "sgx_diffaug")
+        return y
+    if tuple(img_bits.shape) != (B,) or img_bits.dtype != torch.int32 or img_bits.device != x.device:        # ADA: per-image ops
+        raise N.SgxError(f"diffaug: need int32 [{B}] image bits on {x.device}, got {tuple(img_bits.shape)} {img_bits.dtype} on "
+                         f"{img_bits.device}")
+    N.check(L.sgx_diffaug_gated(N.ptr(x), N.ptr(y), N.ptr(u), N.ptr(_c(img_bits)), B, H, W, int(bits), int(adjoint), int(with_bias),
+                                N.ptr(ws), nb, N.stream()), "sgx_diffaug_gated")
     return y
 
 
+# The three functions take an optional ``img_bits`` (int32 [B], from ``ada_gates``; no gradient): given, image b is transformed under
+# img_bits[b] (``sgx_diffaug_gated``) and ``bits`` is the union.  It is saved next to ``u`` and handed down the chain, so every pass of
+# one D evaluation -- adjoint, linear part, the R1 double backward -- sees the gates of its forward.
 class DiffAugFn(Function):
     """y = Mask(Shift(L x + b)) with the draws ``u`` [B,7] (no gradient); backward = the adjoint (DiffAugAdjFn), none when x needs
     no gradient (the D step's fakes)."""
 
     @staticmethod
-    def forward(ctx, x, u, bits):
-        ctx.save_for_backward(u)
+    def forward(ctx, x, u, bits, img_bits=None):
+        ctx.save_for_backward(u, img_bits)
         ctx.bits = bits
-        return _diffaug(x, u, bits, False, True)
+        return _diffaug(x, u, bits, False, True, img_bits)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
-            return None, None, None
-        (u,) = ctx.saved_tensors
-        return _bcall(DiffAugAdjFn, g, u, ctx.bits), None, None
+            return None, None, None, None
+        u, img_bits = ctx.saved_tensors
+        return _bcall(DiffAugAdjFn, g, u, ctx.bits, img_bits), None, None, None
 
 
 class DiffAugAdjFn(Function):
     """A^T g = L(Shift^T(Mask g)); backward = A without the bias (DiffAugLinFn)."""
 
     @staticmethod
-    def forward(ctx, g, u, bits):
-        ctx.save_for_backward(u)
+    def forward(ctx, g, u, bits, img_bits=None):
+        ctx.save_for_backward(u, img_bits)
         ctx.bits = bits
-        return _diffaug(g, u, bits, True, False)
+        return _diffaug(g, u, bits, True, False, img_bits)
 
     @staticmethod
     def backward(ctx, gg):
-        (u,) = ctx.saved_tensors
-        return _bcall(DiffAugLinFn, gg, u, ctx.bits), None, None
+        u, img_bits = ctx.saved_tensors
+        return _bcall(DiffAugLinFn, gg, u, ctx.bits, img_bits), None, None, None
 
 
 class DiffAugLinFn(Function):
     """A x = Mask(Shift(L x)) (the linear part of DiffAugFn); backward = DiffAugAdjFn."""
 
     @staticmethod
-    def forward(ctx, x, u, bits):
-        ctx.save_for_backward(u)
+    def forward(ctx, x, u, bits, img_bits=None):
+        ctx.save_for_backward(u, img_bits)
         ctx.bits = bits
-        return _diffaug(x, u, bits, False, False)
+        return _diffaug(x, u, bits, False, False, img_bits)
 
     @staticmethod
     def backward(ctx, g):
-        (u,) = ctx.saved_tensors
-        return _bcall(DiffAugAdjFn, g, u, ctx.bits), None, None
+        u, img_bits = ctx.saved_tensors
+        return _bcall(DiffAugAdjFn, g, u, ctx.bits, img_bits), None, None, None
+
+
+# ADA (Karras et al., NeurIPS 2020): the gates of one D evaluation and the controller of p, both reading / writing the fp32 [8] state
+# (include/sgx.h) on the device -- no host value of p exists on the step path.
+def _ada_state_ok(state, device, what):
+    if tuple(state.shape) != (8,) or state.dtype != torch.float32 or state.device != device or not state.is_contiguous():
+        raise N.SgxError(f"{what}: need a contiguous fp32 [8] state on {device}, got {tuple(state.shape)} {state.dtype} on {state.device}")
+
+
+def ada_gates(gu, state, bits):
+    """gu fp32 [B,3] uniforms, state fp32 [8] (state[0] = p) -> int32 [B]: ``bits`` & (op k on iff gu[b,k] < p)."""
+    gu = _c(gu)
+    if gu.dim() != 2 or gu.shape[1] != 3 or gu.dtype != torch.float32:
+        raise N.SgxError(f"ada_gates: need fp32 [B,3] uniforms, got {tuple(gu.shape)} {gu.dtype}")
+    _ada_state_ok(state, gu.device, "ada_gates")
+    out = torch.empty(gu.shape[0], dtype=torch.int32, device=gu.device)
+    N.check(N.lib().sgx_ada_gates(N.ptr(gu), N.ptr(state), int(bits), N.ptr(out), gu.shape[0], N.stream()), "sgx_ada_gates")
+    return out
+
+
+def ada_update(real_logits, state, target, adjust_per_image, interval):
+    """One controller call (in place on ``state``): accumulate sign(D(real)), and every ``interval`` calls move p by
+    adjust_per_image * (images counted) towards r_t == target."""
+    lg = _c(real_logits.detach()).reshape(-1)
+    if lg.dtype != torch.float32:
+        raise N.SgxError(f"ada_update: need fp32 logits, got {lg.dtype}")
+    _ada_state_ok(state, lg.device, "ada_update")
+    N.check(N.lib().sgx_ada_update(N.ptr(lg), lg.numel(), N.ptr(state), float(target), float(adjust_per_image), int(interval), N.stream()),
+            "sgx_ada_update")
+    return state

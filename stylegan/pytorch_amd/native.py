@@ -78,6 +78,9 @@ SIGNATURES = {
     "sgx_downsample_fade_rgb": (I, [P, P, I, I, I, F, F, P, P]),
     "sgx_diffaug_ws_bytes": (Z, [I, I, I]),
     "sgx_diffaug": (I, [P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "sgx_ada_gates": (I, [P, P, I, P, I, P]),
+    "sgx_diffaug_gated": (I, [P, P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "sgx_ada_update": (I, [P, I, P, F, F, I, P]),
     "sgx_rgb_out_fade": (I, [P, P, I, I, F, P, P, F, F, P, P, I, I, I, I, I, P]),
     "sgx_rgb_wgrad_ws_bytes": (Z, [Z, I]),
     "sgx_rgb_wgrad": (I, [P, P, P, I, I, F, P, Z, Z, I, I, P]),
