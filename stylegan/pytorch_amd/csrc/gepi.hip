@@ -21,6 +21,7 @@ struct GepiGeom { int cvt, rows, chunk, nchunk; };
 static GepiGeom gepi_geom(int B, int HW, int C, int ve) {
     GepiGeom g;
     int cv = C / ve;
+    if (cv < 1) cv = 1;            // (sgx_gepi_ws_bytes sizes for both vector widths: fp32 with C = 4 has no bf16 vector, and rows divides by cvt)
     g.cvt = cv < 256 ? cv : 256;
     g.rows = 256 / g.cvt;
     static const int rpt_max = [] { const char* e = getenv("SGX_GEPI_RPT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : GEPI_ROWS_PER_THREAD; }();
