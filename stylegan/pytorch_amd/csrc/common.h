@@ -91,6 +91,17 @@ static inline bool sgx_nt_for(double tensor_bytes) {
     static const double min_bytes = [] { const char* e = getenv("SGX_NT_MIN_MB"); const double mb = e ? atof(e) : 192.0; return mb > 0 ? mb * 1e6 : 1e300; }();
     return tensor_bytes >= min_bytes;
 }
+// An integer switch of the environment.  SGX_SWITCH names the accessor of one switch: the value is read at its first
+// call and kept for the process, every use site calls the accessor
+static inline int sgx_env_int(const char* name, int def) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : def;
+}
+#define SGX_SWITCH(fn, name, def) \
+    static int fn() { static const int v = sgx_env_int(name, def); return v; }
+// XCD-band tile order of the persistent convolution grids, both kernel generations.  Measured (round 2): halo
+// over-fetch gone (PMC), 80.8 vs 81.2 ms at batch 32, nothing at batch 4
+inline int sgx_tile_bands_on() { static const int v = sgx_env_int("SGX_TILE_BANDS", 1); return v; }
 __device__ __forceinline__ float to_f(float v) { return v; }
 __device__ __forceinline__ float to_f(bf16_t v) { return bf2f(v); }
 template <typename T> __device__ __forceinline__ T from_f(float v);
@@ -128,6 +139,19 @@ void sgx_set_error(const char* fmt, ...);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 int sgx_ncu();                                             // compute units of the current device (api.hip)
+
+// ---- between the convolution files (geo: 0 = 3x3, 1 = 4x4 stride 2, 2 = 4x4 stride 2 transposed) ---------------------------------
+static inline int sgx_conv_out(int geo, int n) { return geo == 1 ? n / 2 : (geo == 2 ? 2 * n : n); }      // output extent of an input extent
+// conv2.hip, the second-generation bf16 convolutions, for the entry points of conv.hip.  try: *launched = 1 if the kernel ran, 0 leaves the
+// shape to the first generation (variant: -1 = choose, else a probe's choice, see sgx_conv_variant); takes: would try (variant -1) launch?
+int sgx_conv2_try(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act,
+                  const void* mask, int variant, hipStream_t st, int* launched);
+int sgx_conv2_takes(int geo, int B, int H, int W, int Cin, int Cout);
+// wgrad2.hip, the second-generation bf16 weight gradients, for conv.hip: plan = pixel splits (0: the shape stays with wgrad_kernel); launch
+// writes the same per-split partials as wgrad_kernel
+int sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn, int* nct_n, int* nct_k, int* kbw, int* ntiles);
+int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, size_t ws_bytes, int B, int H, int W, int Ck, int Cn,
+                      int want_bias, hipStream_t st, int* nsplit_out);
 
 // ---- per-launch profiler (sgx_prof_* in include/sgx.h) --------------------------------------
 // Every kernel launch of the library goes through sgx_launch.  When profiling is on it is bracketed by two HIP events

@@ -19,15 +19,21 @@
 #include "common.h"
 #include <stdlib.h>
 
-enum { G3X3 = 0, GDOWN = 1, GUP = 2, GUPA = 3 };
-// second-generation bf16 weight-gradient kernels (wgrad2.hip): plan = pixel splits (0: shape stays here); launch writes the
-// same per-split partials as wgrad_kernel below
-int sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn, int* nct_n, int* nct_k, int* kbw, int* ntiles);
-int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, size_t ws_bytes, int B, int H, int W, int Ck, int Cn,
-                      int want_bias, hipStream_t st, int* nsplit_out);
-int sgx_conv2_try(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act,
-                  const void* mask, int variant, hipStream_t st, int* launched);        // conv2.hip
-int sgx_conv2_takes(int geo, int B, int H, int W, int Cin, int Cout);                   // conv2.hip   // GUPA: GUP with all four parity classes in one block (bf16)
+enum { G3X3 = 0, GDOWN = 1, GUP = 2, GUPA = 3 };      // GUPA: GUP with all four parity classes in one block (bf16)
+// (the second-generation kernels of conv2.hip and wgrad2.hip that the entry points below try first: declared in common.h)
+
+// The switches of the forward convolutions.  PERCU: at most this many resident blocks per CU; MAXCT, MAXBP, MINBLOCKS:
+// tuning knobs of pick_cfg; DEEPK, UPA, SPLITK: A/B switches of the rules that read them
+SGX_SWITCH(conv_percu_cap, "SGX_CONV_PERCU", 0)
+SGX_SWITCH(conv_max_ct, "SGX_CONV_MAXCT", 4)
+SGX_SWITCH(conv_max_bp, "SGX_CONV_MAXBP", 256)
+SGX_SWITCH(conv_min_blocks_env, "SGX_CONV_MINBLOCKS", 0)
+SGX_SWITCH(conv_deep_k_on, "SGX_CONV_DEEPK", 1)
+SGX_SWITCH(conv_upa_on, "SGX_CONV_UPA", 1)
+SGX_SWITCH(conv_splitk_env, "SGX_CONV_SPLITK", 1)
+#ifdef SGX_PROBE_BUILD                                  // ablation switches, WRONG results by design: only a probe build (make PROBE=1) reads them
+SGX_SWITCH(conv_dbg, "SGX_CONV_DBG", 0)
+#endif
 
 // LDS operand tiles are arrays of rows (one pixel, or one (tap, output channel) weight row) holding KC channels.
 // rowb_*: row pitch in bytes; load(): the lane's MFMA fragment (k = kk-step, q = lane>>4); lstore(): one 16-byte chunk.
@@ -114,6 +120,17 @@ struct ConvArgs {
     // 0.26-0.6 MB weight slice at ONE CU's load rate (~25 GB/s): 15-36 us for 0.5-5 GFLOP, whatever the K-chunk depth.
     int ksplit; float* kws;
 };
+// The extent of the grid that the tiles cover: the output, for the transposed geometry the coarse input
+static int conv_tile_extent(int geo, int n) { return geo == GUP ? n : sgx_conv_out(geo, n); }
+// geo: G3X3 / GDOWN / GUP.  Every member that is not an argument starts at zero and is set by name where it is needed.
+static ConvArgs conv_args(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act) {
+    ConvArgs a{};
+    a.x = x; a.w = w; a.bias = bias; a.y = y;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;
+    a.OH = sgx_conv_out(geo, H); a.OW = sgx_conv_out(geo, W);
+    a.OHc = conv_tile_extent(geo, H); a.OWc = conv_tile_extent(geo, W);
+    return a;
+}
 
 template <int GEO> struct Geo;
 template <> struct Geo<G3X3> { static constexpr int IS = 1, TK = 3, NCLS = 1; };
@@ -534,10 +551,8 @@ static int launch_conv(ConvArgs& a, int ngroups, hipStream_t st) {
     auto kern = conv_kernel<T, KC, GEO, TH, TW, BP, CT, SK>;
     sgx_lds_opt_in<conv_kernel<T, KC, GEO, TH, TW, BP, CT, SK>>(LDS);
     a.ntiles = ngroups * a.tiles_y * a.tiles_x;
-    // the ablation switches give WRONG results by design: only a probe build (make PROBE=1 -> -DSGX_PROBE_BUILD) reads them
 #ifdef SGX_PROBE_BUILD
-    static const int dbg = [] { const char* e = getenv("SGX_CONV_DBG"); return e ? atoi(e) : 0; }();
-    a.dbg = dbg;
+    a.dbg = conv_dbg();
 #else
     a.dbg = 0;
 #endif
@@ -546,8 +561,7 @@ static int launch_conv(ConvArgs& a, int ngroups, hipStream_t st) {
     static const int resident = [] {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(conv_kernel<T, KC, GEO, TH, TW, BP, CT, SK>), 256, LDS) != hipSuccess || nb < 1) nb = 1;
-        const char* e = getenv("SGX_CONV_PERCU");
-        if (e && atoi(e) > 0 && atoi(e) < nb) nb = atoi(e);
+        if (conv_percu_cap() > 0 && conv_percu_cap() < nb) nb = conv_percu_cap();
         return nb;
     }();
     const int ncu = sgx_ncu();
@@ -556,9 +570,8 @@ static int launch_conv(ConvArgs& a, int ngroups, hipStream_t st) {
     int gx = (ncu * per_cu + yz - 1) / yz;
     if (gx > a.ntiles) gx = a.ntiles;
     if (gx < 1) gx = 1;
-    static const int bands_on = [] { const char* e = getenv("SGX_TILE_BANDS"); return e ? atoi(e) : 1; }();   // measured (round 2): halo over-fetch gone (PMC), 80.8 vs 81.2 ms at batch 32, nothing at batch 4
     a.bands = 0;
-    if (conv_bands_ok<T>(GEO, TH, TW, BP) && bands_on && gx >= 64 && a.ntiles >= 8 * gx) {   // enough tiles per band for the order to matter
+    if (conv_bands_ok<T>(GEO, TH, TW, BP) && sgx_tile_bands_on() && gx >= 64 && a.ntiles >= 8 * gx) {   // enough tiles per band for the order to matter
         gx = gx / 8 * 8;
         a.bands = 1;
     }
@@ -592,9 +605,7 @@ static ConvCfg pick_cfg(int geo, int B, int ohc, int owc, int Cout) {
     const int n = geo == GDOWN ? 4 : (geo == GUPA ? 6 : 8);
     ConvCfg best{0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
-        static const int max_ct = [] { const char* e = getenv("SGX_CONV_MAXCT"); return e ? atoi(e) : 4; }();   // tuning knob
-        static const int max_bp = [] { const char* e = getenv("SGX_CONV_MAXBP"); return e ? atoi(e) : 256; }();
-        if (cand[i][1] > max_ct || cand[i][0] > max_bp) continue;
+        if (cand[i][1] > conv_max_ct() || cand[i][0] > conv_max_bp()) continue;
         if (Cout % (16 * cand[i][1]) != 0) continue;
         ConvCfg c{cand[i][0], cand[i][1], 0, 0, 0};
         tile_shape(c.bp, ohc, owc, c);
@@ -602,8 +613,7 @@ static ConvCfg pick_cfg(int geo, int B, int ohc, int owc, int Cout) {
         best = c;
         const long blocks = (long)((B + c.ni - 1) / c.ni) * ((ohc + c.th - 1) / c.th) * ((owc + c.tw - 1) / c.tw) *
                             (Cout / (16 * c.ct)) * (geo == GUP ? 4 : 1);
-        static const long min_blocks = [] { const char* e = getenv("SGX_CONV_MINBLOCKS"); return e && atoi(e) > 0 ? atol(e) : 512L; }();
-        if (blocks >= min_blocks) break;
+        if (blocks >= (conv_min_blocks_env() > 0 ? conv_min_blocks_env() : 512)) break;
     }
     return best;
 }
@@ -611,8 +621,7 @@ static ConvCfg pick_cfg(int geo, int B, int ohc, int owc, int Cout) {
 // Deep K-chunks (128 input channels per LDS stage) for the layers whose launch is 64-pixel tiles: many input channels, few
 // pixels -- their time is the number of load/barrier/MFMA stages, not bytes or FLOPs.  SGX_CONV_DEEPK=0 switches it off.
 static bool conv_deep_k(int geo, int B, int ohc, int owc, int Cin, int Cout) {
-    static const int on = [] { const char* e = getenv("SGX_CONV_DEEPK"); return e ? atoi(e) : 1; }();
-    if (!on || Cin % 128 != 0 || geo == GDOWN) return false;
+    if (!conv_deep_k_on() || Cin % 128 != 0 || geo == GDOWN) return false;
     const ConvCfg c = pick_cfg(geo, B, ohc, owc, Cout);
     return c.bp == 64 && (c.ct == 1 || c.ct == 2);
 }
@@ -669,8 +678,7 @@ static int dispatch_conv(ConvArgs& a, int dtype, hipStream_t st) {
             }
         }
         if constexpr (GEO == GUP) {
-            static const int fuse = [] { const char* e = getenv("SGX_CONV_UPA"); return e ? atoi(e) : 1; }();   // A/B switch
-            if (fuse) {
+            if (conv_upa_on()) {
                 if (a.Cin % 32 == 0) return dispatch_cfg<bf16_t, 32, GUPA, SK>(a, st);
                 return dispatch_cfg<bf16_t, 16, GUPA, SK>(a, st);
             }
@@ -712,7 +720,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish(const float* __restric
 // How many ways a bf16 launch splits its reduction (0 = not at all): only launches that stay with this file's kernel, only when their grid
 // leaves most of the chip idle, a divisor of the K-chunk count, as many blocks as ~2 per CU, at most 8 (the finish pass reads ksplit partials).
 static int conv_splitk_plan(int geo, int B, int H, int W, int Cin, int Cout, int dtype) {
-    static const int on = [] { const char* e = getenv("SGX_CONV_SPLITK"); const int v = e ? atoi(e) : 1; return v < 0 ? 1 : v; }();      // A/B switch (0 = off; n > 1 = at most n ways)
+    const int on = conv_splitk_env() < 0 ? 1 : conv_splitk_env();      // 0 = off; n > 1 = at most n ways
     if (!on || dtype != SGX_BF16 || geo < 0 || geo > 2 || Cin % 16 || Cout % 16) return 0;
     // Measured alone on the MI355X (tools/splitk_probe.py, batch 4, 512 channels; both launches of the split form): stride-2 16^2 -> 8^2 23.1 ->
     // 17.0 us, 8^2 -> 4^2 21.2 -> 11.4 us; 3x3 at 4^2 / 8^2 11.3 -> 9.7 / 11.7 -> 10.8 us; transposed 4^2 -> 8^2 8.2 -> 9.1 us (worse).  The 3x3 and
@@ -722,7 +730,7 @@ static int conv_splitk_plan(int geo, int B, int H, int W, int Cin, int Cout, int
     // and are no longer compiled: 84 instantiations and two minutes of build time for nothing.)
     if (geo != GDOWN) return 0;
     if (sgx_conv2_takes(geo, B, H, W, Cin, Cout)) return 0;
-    const int ohc = geo == GDOWN ? H / 2 : H, owc = geo == GDOWN ? W / 2 : W;
+    const int ohc = conv_tile_extent(geo, H), owc = conv_tile_extent(geo, W);
     // the instantiation dispatch_conv picks for this shape: deep K-chunks first, else (transposed) the all-class kernel
     const bool deep = geo != GDOWN && conv_deep_k(geo, B, ohc, owc, Cin, Cout);
     const ConvCfg c = pick_cfg((geo == GUP && !deep) ? GUPA : geo, B, ohc, owc, Cout);
@@ -741,7 +749,7 @@ static int conv_splitk_plan(int geo, int B, int H, int W, int Cin, int Cout, int
 extern "C" size_t sgx_conv_splitk_ws_bytes(int geo, int B, int H, int W, int Cin, int Cout, int dtype) {
     const int ks = conv_splitk_plan(geo, B, H, W, Cin, Cout, dtype);
     if (!ks) return 0;
-    const size_t opix = geo == GDOWN ? (size_t)B * (H / 2) * (W / 2) : (geo == GUP ? (size_t)B * 4 * H * W : (size_t)B * H * W);
+    const size_t opix = (size_t)B * sgx_conv_out(geo, H) * sgx_conv_out(geo, W);
     return (size_t)ks * opix * Cout * sizeof(float);
 }
 // sgx_conv3x3 / sgx_conv4x4s2_down / sgx_conv4x4s2_up (geo 0 / 1 / 2) of a shape for which sgx_conv_splitk_ws_bytes is not 0, with the
@@ -754,9 +762,9 @@ extern "C" int sgx_conv_splitk(int geo, const void* x, const void* w, const floa
     SGX_REQUIRE(geo == G3X3 || !mask, SGX_EINVAL, "conv_splitk: the output mask belongs to the 3x3 geometry");
     SGX_REQUIRE(geo != GDOWN || (H % 2 == 0 && W % 2 == 0), SGX_EINVAL, "conv_splitk: odd input size");
     hipStream_t st = (hipStream_t)stream;
-    const int OH = geo == GDOWN ? H / 2 : (geo == GUP ? 2 * H : H), OW = geo == GDOWN ? W / 2 : (geo == GUP ? 2 * W : W);
-    ConvArgs a{x, w, nullptr, y, B, H, W, OH, OW, geo == GUP ? H : OH, geo == GUP ? W : OW, Cin, Cout, SGX_ACT_NONE, 0, 0, 0, nullptr};
+    ConvArgs a = conv_args(geo, x, w, nullptr, y, B, H, W, Cin, Cout, SGX_ACT_NONE);      // (bias, activation and mask: the finishing launch)
     a.ksplit = ks; a.kws = static_cast<float*>(ws);
+    const int OH = a.OH, OW = a.OW;
     const double taps = geo == G3X3 ? 9.0 : 16.0, opix = (double)B * OH * OW, macs = geo == GUP ? taps / 4.0 : taps;
     SGX_NOTE(2.0 * macs * Cin * Cout * opix, 2.0 * ((double)B * H * W * Cin + opix * Cout + taps * Cin * Cout) + 4.0 * ks * opix * Cout, "conv%c/k%d B%d %dx%d %d->%d",
              geo == G3X3 ? 'S' : (geo == GDOWN ? 'D' : 'U'), ks, B, H, W, Cin, Cout);
@@ -774,51 +782,48 @@ extern "C" int sgx_conv_splitk(int geo, const void* x, const void* w, const floa
 
 extern "C" int sgx_conv_config(int geo, int B, int H, int W, int Cin, int Cout, int dtype, int* cfg5) {
     SGX_REQUIRE(geo >= 0 && geo <= 2 && cfg5, SGX_EINVAL, "conv_config: bad args");
-    const int ohc = geo == GDOWN ? H / 2 : H, owc = geo == GDOWN ? W / 2 : W;
+    const int ohc = conv_tile_extent(geo, H), owc = conv_tile_extent(geo, W);
     const ConvCfg c = pick_cfg(geo, B, ohc, owc, Cout);
     cfg5[0] = dtype == SGX_F32 ? 16 : (conv_deep_k(geo, B, ohc, owc, Cin, Cout) ? 128 : (Cin % 32 == 0 ? 32 : 16));
     cfg5[1] = c.th; cfg5[2] = c.tw; cfg5[3] = c.bp; cfg5[4] = c.ct;
     return 0;
 }
 
-extern "C" int sgx_conv3x3(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin,
-                           int Cout, int act, const void* mask, int dtype, void* stream) {
-    ConvArgs a{x, w, bias, y, B, H, W, H, W, H, W, Cin, Cout, act, 0, 0, 0, mask};
-    const double es = dtype == SGX_F32 ? 4 : 2;
-    SGX_NOTE(2.0 * 9 * Cin * Cout * B * H * W, es * ((double)B * H * W * (Cin + Cout) + 9.0 * Cin * Cout), "convS B%d %dx%d %d->%d", B, H, W, Cin, Cout);
-    if (dtype == SGX_BF16) {                                   // second-generation kernel (conv2.hip) where it applies
+// A forward convolution: bf16 shapes go to the second-generation kernel (conv2.hip) where it applies, everything else to conv_kernel
+template <int GEO>
+static int conv_forward(ConvArgs& a, int dtype, hipStream_t st) {
+    if (dtype == SGX_BF16) {
         int launched = 0;
-        const int rc = sgx_conv2_try(G3X3, x, w, bias, y, B, H, W, Cin, Cout, act, mask, -1, (hipStream_t)stream, &launched);
+        const int rc = sgx_conv2_try(GEO, a.x, a.w, a.bias, a.y, a.B, a.H, a.W, a.Cin, a.Cout, a.act, a.mask, -1, st, &launched);
         if (rc || launched) return rc;
     }
-    return dispatch_conv<G3X3>(a, dtype, (hipStream_t)stream);
+    return dispatch_conv<GEO>(a, dtype, st);
+}
+
+extern "C" int sgx_conv3x3(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin,
+                           int Cout, int act, const void* mask, int dtype, void* stream) {
+    ConvArgs a = conv_args(G3X3, x, w, bias, y, B, H, W, Cin, Cout, act);
+    a.mask = mask;
+    const double es = dtype == SGX_F32 ? 4 : 2;
+    SGX_NOTE(2.0 * 9 * Cin * Cout * B * H * W, es * ((double)B * H * W * (Cin + Cout) + 9.0 * Cin * Cout), "convS B%d %dx%d %d->%d", B, H, W, Cin, Cout);
+    return conv_forward<G3X3>(a, dtype, (hipStream_t)stream);
 }
 
 extern "C" int sgx_conv4x4s2_down(const void* x, const void* w, const float* bias, void* y, int B, int H, int W,
                                   int Cin, int Cout, int act, int dtype, void* stream) {
     SGX_REQUIRE(H % 2 == 0 && W % 2 == 0, SGX_EINVAL, "conv4x4s2_down: odd input size");
-    ConvArgs a{x, w, bias, y, B, H, W, H / 2, W / 2, H / 2, W / 2, Cin, Cout, act, 0, 0};
+    ConvArgs a = conv_args(GDOWN, x, w, bias, y, B, H, W, Cin, Cout, act);
     const double es = dtype == SGX_F32 ? 4 : 2;
     SGX_NOTE(2.0 * 16 * Cin * Cout * B * (H / 2) * (W / 2), es * ((double)B * H * W * (Cin + Cout / 4.0) + 16.0 * Cin * Cout), "convD B%d %dx%d %d->%d", B, H, W, Cin, Cout);
-    if (dtype == SGX_BF16) {
-        int launched = 0;
-        const int rc = sgx_conv2_try(GDOWN, x, w, bias, y, B, H, W, Cin, Cout, act, nullptr, -1, (hipStream_t)stream, &launched);
-        if (rc || launched) return rc;
-    }
-    return dispatch_conv<GDOWN>(a, dtype, (hipStream_t)stream);
+    return conv_forward<GDOWN>(a, dtype, (hipStream_t)stream);
 }
 
 extern "C" int sgx_conv4x4s2_up(const void* x, const void* w, void* y, int B, int H, int W, int Cin, int Cout,
                                 int dtype, void* stream) {
-    ConvArgs a{x, w, nullptr, y, B, H, W, 2 * H, 2 * W, H, W, Cin, Cout, SGX_ACT_NONE, 0, 0};
+    ConvArgs a = conv_args(GUP, x, w, nullptr, y, B, H, W, Cin, Cout, SGX_ACT_NONE);
     const double es = dtype == SGX_F32 ? 4 : 2;
     SGX_NOTE(2.0 * 16 * Cin * Cout * B * H * W, es * ((double)B * H * W * (Cin + 4.0 * Cout) + 16.0 * Cin * Cout), "convU B%d %dx%d %d->%d", B, H, W, Cin, Cout);
-    if (dtype == SGX_BF16) {
-        int launched = 0;
-        const int rc = sgx_conv2_try(GUP, x, w, nullptr, y, B, H, W, Cin, Cout, SGX_ACT_NONE, nullptr, -1, (hipStream_t)stream, &launched);
-        if (rc || launched) return rc;
-    }
-    return dispatch_conv<GUP>(a, dtype, (hipStream_t)stream);
+    return conv_forward<GUP>(a, dtype, (hipStream_t)stream);
 }
 
 extern "C" int sgx_conv_variant(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin,
@@ -826,8 +831,8 @@ extern "C" int sgx_conv_variant(int geo, const void* x, const void* w, const flo
     SGX_REQUIRE(geo >= 0 && geo <= 2, SGX_EINVAL, "conv_variant: bad geometry %d", geo);
     SGX_REQUIRE(geo != GDOWN || (H % 2 == 0 && W % 2 == 0), SGX_EINVAL, "conv_variant: odd input size");
     SGX_REQUIRE(geo != GUP || (!bias && act == SGX_ACT_NONE), SGX_EINVAL, "conv_variant: the transposed convolution has no fused bias / activation");
-    const int OH = geo == GDOWN ? H / 2 : (geo == GUP ? 2 * H : H), OW = geo == GDOWN ? W / 2 : (geo == GUP ? 2 * W : W);
-    ConvArgs a{x, w, bias, y, B, H, W, OH, OW, geo == GUP ? H : OH, geo == GUP ? W : OW, Cin, Cout, act, 0, 0};
+    ConvArgs a = conv_args(geo, x, w, bias, y, B, H, W, Cin, Cout, act);
+    const int OH = a.OH, OW = a.OW;
     const double es = dtype == SGX_F32 ? 4 : 2, taps = geo == G3X3 ? 9 : 16, npix = (double)B * (geo == GDOWN ? OH * OW : H * W);
     SGX_NOTE(2.0 * taps * Cin * Cout * npix, es * ((double)B * (H * W * Cin + OH * OW * Cout) + taps * Cin * Cout), "conv%c/v%d B%d %dx%d %d->%d", "SDU"[geo], variant, B, H, W, Cin, Cout);
     if (variant == 0) {

@@ -797,8 +797,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv2_kernel(Conv2Args a) {
     }
 }
 
-static int conv2_ncu() { return sgx_ncu(); }
-
 // =====================================================================================================================================
 // conv3_kernel (round 5): the same convolution, the same LDS image, the same accumulation order (bit-identical results) -- with the
 // LDS -> MFMA pipeline written by hand.  What the round-4 counters and the disassembly of conv2_kernel<S,8,2> say about its K-step:
@@ -1309,80 +1307,105 @@ __global__ __launch_bounds__(NW * 64, UB == 2 ? 2 * NW / 4 : NW / 4) void conv3_
     }
 }
 
+// =====================================================================================================================================
+// Host side.  The switches of this file: defaults are the measured winners, the others stay for A/B runs and probes.
+SGX_SWITCH(conv2_on_bits, "SGX_CONV2", 15)              // bit 0: S, 1: D, 2: U take this kernel; bit 3: the 16-channel variants; bit 4: also the transposed 32->16 one
+SGX_SWITCH(conv2_force_nw, "SGX_CONV2_NW", 0)           // 4 / 8: that block whatever the grid
+SGX_SWITCH(conv2_force_nw16, "SGX_CONV2_NW16", 0)       // the same for the 16-channel variants
+SGX_SWITCH(conv2_small_on, "SGX_CONV2_SMALL", 1)        // 0 = the round-2 shape rule (no 32-channel blocks for small grids)
+SGX_SWITCH(conv2_bpc_max, "SGX_CONV2_BPC", 2)           // resident blocks per CU of the half-width stages, at most
+SGX_SWITCH(conv_nt_bits, "SGX_CONV_NT", 0)              // probe: nontemporal hints, bit 0 the output stores, bit 1 the patch DMA
+// measured on one box (round 6, default bench line, two interleaved rounds): register store 291.2 / 291.4 img/s at batch 4 and 523.0 / 521.4 at
+// batch 32, LDS-transposed store 292.8 / 293.9 and 525.0 / 525.4 -- whole 64-byte pixels per store instruction win
+SGX_SWITCH(convu_regstore, "SGX_CONVU_REGSTORE", 0)
+SGX_SWITCH(conv_upblur_on, "SGX_CONV_UPBLUR", 1)        // sgx_conv_upblur_ok
+SGX_SWITCH(upblur_bpc, "SGX_UPBLUR_BPC", 1)             // 2: two compact 4-wave blocks per CU (round 6)
+SGX_SWITCH(conv_up_blur_on, "SGX_CONV_UP_BLUR", 1)      // sgx_conv4x4s2_up_blur_ok
+SGX_SWITCH(signbits_on, "SGX_SIGNBITS", 1)              // sgx_conv3x3_signbits_ok
+SGX_SWITCH(fuse_fade_on, "SGX_FUSE_FADE", 1)            // sgx_conv4x4s2_down_fade_ok
+#ifdef SGX_PROBE_BUILD                                  // DMA ablations of conv3_kernel (WRONG results by design): probe builds only (make PROBE=1)
+SGX_SWITCH(conv3_dbg, "SGX_CONV3_DBG", 0)
+#endif
+
+// geo: C2_S / C2_D / C2_U.  Every member that is not an argument starts at zero; the launchers fill the grid, an entry point sets what its
+// epilogue reads by name.
+static Conv2Args conv2_args(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act) {
+    Conv2Args a{};
+    a.x = static_cast<const bf16_t*>(x); a.w = static_cast<const bf16_t*>(w); a.bias = bias; a.y = static_cast<bf16_t*>(y);
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;
+    a.OH = sgx_conv_out(geo, H); a.OW = sgx_conv_out(geo, W);
+    return a;
+}
+
+// The persistent grid of one launch, for conv2_kernel and conv3_kernel alike.  What the instantiation contributes:
+struct Conv2Block {
+    int geo, th, lds, nw;   // tile grid (C2_S: the image, C2_D: the output, C2_U: the coarse input) and tile height (a tile is 32 wide); LDS bytes; waves
+    int kc, bco;            // input channels per K-step; output channels that a block really stores (CO16: 16 of its 32)
+    int ub;                 // conv3_kernel<UB>: 2 = the compact block
+    bool overlap;           // EPI_BLUR: tiles overlap by one coarse row / column, steps th - 1 and 31
+};
+// fills tiles_x, tiles_y, ntiles, ncb, nslots and bands of `a` and returns the number of blocks
+static unsigned conv2_plan_grid(Conv2Args& a, const Conv2Block& k) {
+    const int gh = k.geo == C2_D ? a.OH : a.H, gw = k.geo == C2_D ? a.OW : a.W;
+    a.tiles_x = (gw + 31) / 32; a.tiles_y = (gh + k.th - 1) / k.th;
+    if (k.overlap) {
+        a.tiles_y = gh <= k.th ? 1 : (gh - k.th + k.th - 2) / (k.th - 1) + 1;
+        a.tiles_x = gw <= 32 ? 1 : (gw - 32 + 30) / 31 + 1;
+    }
+    a.ntiles = a.B * a.tiles_y * a.tiles_x;
+    a.ncb = a.Cout / k.bco;
+    // resident blocks per CU: one for the round-2 instantiations (their LDS stages fill the CU); the half-width stages of the
+    // 16-channel layers leave room for two (LDS <= 80 KB per block, <= 128 registers), so that one block's store epilogue
+    // overlaps the other's loads; the compact conv3 block is built for two
+    int bpc = 1;
+    if (k.kc == 16) {
+        bpc = (160 * 1024) / k.lds;
+        if (bpc > 32 / k.nw) bpc = 32 / k.nw;
+        if (bpc > conv2_bpc_max()) bpc = conv2_bpc_max();
+        if (bpc < 1) bpc = 1;
+    } else if (k.ub == 2) {
+        bpc = (160 * 1024) / k.lds;
+    }
+    int per = sgx_ncu() * bpc / (8 * a.ncb);             // tile slots per XCD
+    const int need = (a.ntiles + 7) / 8;
+    if (per > need) per = need;
+    if (per < 1) per = 1;
+    a.nslots = per * 8;
+    a.bands = (sgx_tile_bands_on() && a.ntiles >= 8 * a.nslots) ? 1 : 0;      // enough tiles per slot for the order to matter
+    return (unsigned)(a.ncb * a.nslots);
+}
+// nontemporal hints of a launch whose output has this many bytes (Conv2Args::nt)
+static int conv2_nt(double out_bytes) { return sgx_nt_for(out_bytes) ? conv_nt_bits() : 0; }
+
 template <int GEO, int NW, int MF, int RPW, int PD, int DIL, int UB = 0>
 static int launch_conv3(Conv2Args& a, hipStream_t st) {
     using L = C3Lds<GEO, NW, MF, RPW>;
     constexpr int LDS = UB == 2 ? L::TOTAL - L::W_BYTES : L::TOTAL;      // (UB == 2: no second weight region)
-    constexpr int BPC = UB == 2 ? (160 * 1024) / LDS : 1;                // resident blocks per CU the launch is sized for
-    static_assert(LDS <= 160 * 1024 && BPC >= 1 && (UB != 2 || BPC == 2), "LDS budget");
+    static_assert(LDS <= 160 * 1024 && (UB != 2 || (160 * 1024) / LDS == 2), "LDS budget");      // (UB == 2: sized for two resident blocks per CU)
     auto kern = conv3_kernel<GEO, NW, MF, RPW, PD, DIL, UB>;
     sgx_lds_opt_in<conv3_kernel<GEO, NW, MF, RPW, PD, DIL, UB>>(LDS);
-    const int gh = GEO == C2_D ? a.OH : a.H, gw = GEO == C2_D ? a.OW : a.W;
-    a.tiles_x = (gw + 31) / 32; a.tiles_y = (gh + L::TH - 1) / L::TH;
-    a.ntiles = a.B * a.tiles_y * a.tiles_x;
-    a.ncb = a.Cout / L::BCO;
-    {
-        static const int cnt = [] { const char* e = getenv("SGX_CONV_NT"); return e ? atoi(e) : 0; }();      // probe: bit 0 stores, bit 1 patch loads
-        a.nt = sgx_nt_for(2.0 * a.B * a.OH * a.OW * (UB ? 16 : a.Cout)) ? cnt : 0;
-    }
-    int per = sgx_ncu() * BPC / (8 * a.ncb);
-    const int need = (a.ntiles + 7) / 8;
-    if (per > need) per = need;
-    if (per < 1) per = 1;
-    a.nslots = per * 8;
-    static const int bands_on = [] { const char* e = getenv("SGX_TILE_BANDS"); return e ? atoi(e) : 1; }();
-    a.bands = (bands_on && a.ntiles >= 8 * a.nslots) ? 1 : 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * a.ncb * per)), dim3(NW * 64), LDS, st, a);
+    const unsigned blocks = conv2_plan_grid(a, Conv2Block{GEO, L::TH, LDS, NW, 32, L::BCO, UB, false});
+    a.nt = conv2_nt(2.0 * a.B * a.OH * a.OW * (UB ? 16 : a.Cout));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NW * 64), LDS, st, a);
     SGX_LAUNCH_CHECK("conv3_kernel");
     return 0;
 }
 
+// plan_only: fill the grid members of `a` and return before anything touches the device (sgx_conv3x3_stats_nparts)
 template <int GEO, int NW, int MF, int KC = 32, bool CO16 = false, int EPI = EPI_NONE>
-static int launch_conv2(Conv2Args& a, hipStream_t st) {
+static int launch_conv2(Conv2Args& a, hipStream_t st, bool plan_only = false) {
     using L = C2Lds<GEO, NW, MF, KC>;
     constexpr int LDS = L::TOTAL + ((EPI != EPI_NONE || GEO == C2_D) ? 1024 : 0);      // + the epilogue's coefficient table (statistics; residual in the store)
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    auto kern = conv2_kernel<GEO, NW, MF, KC, CO16, EPI>;
-    sgx_lds_opt_in<conv2_kernel<GEO, NW, MF, KC, CO16, EPI>>(LDS);
-    const int gh = GEO == C2_D ? a.OH : a.H, gw = GEO == C2_D ? a.OW : a.W;       // the tile grid
-    a.tiles_x = (gw + 31) / 32; a.tiles_y = (gh + L::TH - 1) / L::TH;
-    if constexpr (EPI == EPI_BLUR) {              // tiles overlap by one coarse row / column: steps TH - 1 and 31
-        a.tiles_y = gh <= L::TH ? 1 : (gh - L::TH + L::TH - 2) / (L::TH - 1) + 1;
-        a.tiles_x = gw <= 32 ? 1 : (gw - 32 + 30) / 31 + 1;
-    }
-    a.ntiles = a.B * a.tiles_y * a.tiles_x;
-    a.ncb = CO16 ? 1 : a.Cout / L::BCO;
-    {
-        static const int cnt = [] { const char* e = getenv("SGX_CONV_NT"); return e ? atoi(e) : 0; }();      // probe: bit 0 stores, bit 1 patch loads
-        a.nt = sgx_nt_for(2.0 * a.B * a.OH * a.OW * (CO16 ? 16 : a.Cout)) ? cnt : 0;
-    }
-    if constexpr (GEO == C2_U && EPI == EPI_NONE) {
-        // A/B switch; measured on one box (round 6, default bench line, two interleaved rounds): register store 291.2 / 291.4 img/s at batch 4 and
-        // 523.0 / 521.4 at batch 32, LDS-transposed store 292.8 / 293.9 and 525.0 / 525.4 -- whole 64-byte pixels per store instruction win
-        static const int ureg = [] { const char* e = getenv("SGX_CONVU_REGSTORE"); return e ? atoi(e) : 0; }();
-        a.ureg = ureg;
-    }
-    // resident blocks per CU: one for the round-2 instantiations (their LDS stages fill the CU); the half-width stages of the
-    // 16-channel layers leave room for two (LDS <= 80 KB per block, <= 128 registers), so that one block's store epilogue
-    // overlaps the other's loads
-    int bpc = 1;
-    if constexpr (KC == 16) {
-        static const int bpc_max = [] { const char* e = getenv("SGX_CONV2_BPC"); return e ? atoi(e) : 2; }();   // A/B
-        bpc = (160 * 1024) / LDS;
-        if (bpc > 32 / NW) bpc = 32 / NW;
-        if (bpc > bpc_max) bpc = bpc_max;
-        if (bpc < 1) bpc = 1;
-    }
-    int per = conv2_ncu() * bpc / (8 * a.ncb);           // tile slots per XCD
-    const int need = (a.ntiles + 7) / 8;
-    if (per > need) per = need;
-    if (per < 1) per = 1;
-    a.nslots = per * 8;
-    static const int bands_on = [] { const char* e = getenv("SGX_TILE_BANDS"); return e ? atoi(e) : 1; }();   // measured (round 2): halo over-fetch gone (PMC), 80.8 vs 81.2 ms at batch 32, nothing at batch 4
-    a.bands = (bands_on && a.ntiles >= 8 * a.nslots) ? 1 : 0;      // enough tiles per slot for the order to matter
+    const unsigned blocks = conv2_plan_grid(a, Conv2Block{GEO, L::TH, LDS, NW, KC, CO16 ? 16 : L::BCO, 0, EPI == EPI_BLUR});
     if constexpr (EPI == EPI_STATS)
         SGX_REQUIRE(a.part_slots == 0 || a.part_slots == a.nslots, SGX_EINVAL, "conv2 statistics: partials sized for %d tile slots, the launch uses %d", a.part_slots, a.nslots);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * a.ncb * per)), dim3(NW * 64), LDS, st, a);
+    if (plan_only) return 0;
+    auto kern = conv2_kernel<GEO, NW, MF, KC, CO16, EPI>;
+    sgx_lds_opt_in<conv2_kernel<GEO, NW, MF, KC, CO16, EPI>>(LDS);
+    a.nt = conv2_nt(2.0 * a.B * a.OH * a.OW * (CO16 ? 16 : a.Cout));
+    if constexpr (GEO == C2_U && EPI == EPI_NONE) a.ureg = convu_regstore();
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NW * 64), LDS, st, a);
     SGX_LAUNCH_CHECK("conv2_kernel");
     return 0;
 }
@@ -1395,10 +1418,11 @@ static Conv2Pick conv2_pick(int geo, int B, int H, int W, int Cin, int Cout, int
     // bit 0: S, 1: D, 2: U.  All three on: profiles/r02_conv2_probe.txt (S) and r02_conv2_probe_DU.txt (D, U) -- the shape
     // heuristics below reproduce the per-shape winner of those tables.  bit 3: the 16-channel variants (round 3); bit 4: also the
     // transposed 32->16 one.
-    static const int on = [] { const char* e = getenv("SGX_CONV2"); return e ? atoi(e) : 15; }();
+    const int on = conv2_on_bits(), ncu = sgx_ncu();
     const Conv2Pick none{0, false, false};
     if (variant < 0 && !((on >> geo) & 1)) return none;
     const int gw = geo == C2_D ? W / 2 : W, gh = geo == C2_D ? H / 2 : H;
+    const long t8 = (long)B * ((gh + 15) / 16) * (gw / 32), t4 = (long)B * ((gh + 7) / 8) * (gw / 32);      // tiles of the 8- / 4-wave block
     const bool kc16 = Cin == 16, co16 = Cout == 16;
     if (kc16 || co16) {
         // the 16-channel layers: 3x3 16->16, stride-2 16->32, transposed 32->16 (and nothing else: the networks have no others)
@@ -1410,44 +1434,32 @@ static Conv2Pick conv2_pick(int geo, int B, int H, int W, int Cin, int Cout, int
         // transposed 32->16 @512^2 stays with the first generation (338 vs 384 us: half of every MFMA is padding AND the
         // full-width stage leaves one block per CU) unless bit 4 of SGX_CONV2 asks for it
         if (variant < 0 && geo == C2_U && !(on & 16) && !allow_u16) return none;
-        const long blocks4 = (long)B * ((gh + 7) / 8) * (gw / 32), blocks8 = (long)B * ((gh + 15) / 16) * (gw / 32);
-        if (variant < 0 && blocks4 < conv2_ncu()) return none;
-        static const int force16 = [] { const char* e = getenv("SGX_CONV2_NW16"); return e ? atoi(e) : 0; }();
-        return Conv2Pick{variant > 0 ? variant : (force16 ? force16 : (blocks8 >= 2 * conv2_ncu() ? 8 : 4)), false, true};
+        if (variant < 0 && t4 < ncu) return none;
+        const int force16 = conv2_force_nw16();
+        return Conv2Pick{variant > 0 ? variant : (force16 ? force16 : (t8 >= 2 * ncu ? 8 : 4)), false, true};
     }
     const int bco = (geo == C2_S && Cout % 64 == 0) ? 64 : 32;       // (3x3 with 32 output channels: the MF = 1 block)
     if (Cin % 32 != 0 || Cout % bco != 0 || gw % 32 != 0 || Cout / bco > 32 || gh < 1 || (geo == C2_D && ((H | W) & 1))) return none;
     bool mf2 = geo != C2_U && Cout % 64 == 0;
     if (variant < 0 && geo == C2_D && !mf2) return none;   // 32-channel stride-2 blocks: measured no better than the first generation
-    static const int force_nw = [] { const char* e = getenv("SGX_CONV2_NW"); return e ? atoi(e) : 0; }();
-    if (geo == C2_S && mf2 && variant < 0 && !force_nw) {
+    const int force_nw = conv2_force_nw(), c64 = Cout / 64, c32 = Cout / 32;
+    if (mf2 && variant < 0 && !force_nw && conv2_small_on() && t8 * c64 < ncu) {
         // small grids (batch 4 at 32^2..64^2): the 32-channel block doubles the block count.  Measured alone (round 6, tools/conv2_probe.py
         // variants 22 / 23, bit-identical outputs): batch 4, 64^2 256->256: (8 waves, 64 ch) 128 blocks 33.0 us, (4, 64) 256 blocks 29.3,
         // (8, 32) 256 blocks 24.0, (4, 32) 512 blocks 31.9; 32^2 512->512: first generation 36.4, (4, 64) 48.0, (8, 32) 37.3, (4, 32) 256
-        // blocks 31.1; batch 8, 32^2: (4, 64) 52.4, (8, 32) 44.5, (4, 32) 58.2 -- the first shape in this order that fills the chip
-        static const int small = [] { const char* e = getenv("SGX_CONV2_SMALL"); return e ? atoi(e) : 1; }();     // A/B: 0 = the round-2 rule
-        const long t8 = (long)B * ((gh + 15) / 16) * (gw / 32), t4 = (long)B * ((gh + 7) / 8) * (gw / 32);
-        const int c64 = Cout / 64, c32 = Cout / 32, ncu = conv2_ncu();
-        if (small && t8 * c64 < ncu) {
-            if (t8 * c32 >= ncu) return Conv2Pick{8, false, false};
-            if (t4 * c64 >= ncu) return Conv2Pick{4, true, false};
-            if (t4 * c32 >= ncu) return Conv2Pick{4, false, false};
-            return none;
-        }
-    }
-    if (geo == C2_D && mf2 && variant < 0 && !force_nw) {
-        // the same for the stride-2 geometry, where only (8 waves, 32 channels) ever beat the round-2 choice: batch 4, 128^2 128->256:
+        // blocks 31.1; batch 8, 32^2: (4, 64) 52.4, (8, 32) 44.5, (4, 32) 58.2 -- the first shape in this order that fills the chip.
+        // (4 waves, 64 channels) has no place in that order: Cout % 64 == 0 here, so c32 = 2 c64, and ceil(gh / 8) <= 2 ceil(gh / 16) gives
+        // t4 <= 2 t8, hence t4 c64 <= t8 c32 -- wherever it would fill the chip, (8, 32) one step earlier already does.
+        // The same for the stride-2 geometry, where only (8 waves, 32 channels) ever beat the round-2 choice: batch 4, 128^2 128->256:
         // (4, 64) 33.6 us, first generation 33.4, (8, 32) 28.5 (the other small-grid shapes: (8, 64) or the first generation stay best)
-        static const int small = [] { const char* e = getenv("SGX_CONV2_SMALL"); return e ? atoi(e) : 1; }();
-        const long t8 = (long)B * ((gh + 15) / 16) * (gw / 32);
-        if (small && t8 * (Cout / 64) < conv2_ncu() && t8 * (Cout / 32) >= conv2_ncu()) return Conv2Pick{8, false, false};
+        if (t8 * c32 >= ncu) return Conv2Pick{8, false, false};
+        if (geo == C2_S) return t4 * c32 >= ncu ? Conv2Pick{4, false, false} : none;
     }
-    const int cbs = Cout / (mf2 ? 64 : 32);
-    const long blocks8 = (long)B * ((gh + 15) / 16) * (gw / 32) * cbs, blocks4 = (long)B * ((gh + 7) / 8) * (gw / 32) * cbs;
+    const long blocks8 = t8 * (mf2 ? c64 : c32), blocks4 = t4 * (mf2 ? c64 : c32);
     // measured (profiles/r02_conv2_probe.txt): the 8-wave block wins once its 512-pixel tiles fill the chip, the 4-wave
     // block (256-pixel tiles) down to one block per CU, below that the first-generation kernel's 64-pixel tiles do
-    if (variant < 0 && !force_nw && blocks4 < conv2_ncu()) return none;
-    return Conv2Pick{variant > 0 ? variant : (force_nw ? force_nw : (blocks8 >= conv2_ncu() ? 8 : 4)), mf2, false};
+    if (variant < 0 && !force_nw && blocks4 < ncu) return none;
+    return Conv2Pick{variant > 0 ? variant : (force_nw ? force_nw : (blocks8 >= ncu ? 8 : 4)), mf2, false};
 }
 
 // conv3_kernel by configuration id (sgx_conv_variant 30 + id): 0: 8 waves x 2 rows, fragments one sub-step ahead; 1: two ahead;
@@ -1562,8 +1574,7 @@ extern "C" int sgx_pack_upblur(const float* w, void* wc, int O, int I, int mode,
     return 0;
 }
 extern "C" int sgx_conv_upblur_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
-    static const int on = [] { const char* e = getenv("SGX_CONV_UPBLUR"); return e ? atoi(e) : 1; }();   // A/B switch
-    return on && dtype == SGX_BF16 && Cin == 32 && Cout == 16 && W % 32 == 0 && B > 0 && H > 0 ? 1 : 0;
+    return conv_upblur_on() && dtype == SGX_BF16 && Cin == 32 && Cout == 16 && W % 32 == 0 && B > 0 && H > 0 ? 1 : 0;
 }
 extern "C" int sgx_conv_upblur(const void* x, const void* wc, void* y, const void* maskbits, int B, int H, int W, int Cin, int Cout, int dtype,
                                void* stream) {
@@ -1572,97 +1583,73 @@ extern "C" int sgx_conv_upblur(const void* x, const void* wc, void* y, const voi
                 "conv_upblur: shape B%d %dx%d %d->%d dtype %d has no kernel (sgx_conv_upblur_ok == 0)", B, H, W, Cin, Cout, dtype);
     SGX_NOTE(2.0 * 36 * Cin * Cout * B * H * W, 2.0 * ((double)B * H * W * (Cin + 4.0 * Cout) + 36.0 * Cin * Cout) + (maskbits ? 0.5 * B * H * W * Cout : 0.0),
              "convU*blur%s B%d %dx%d %d->%d", maskbits ? "*bits" : "", B, H, W, Cin, Cout);
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(wc), nullptr, static_cast<bf16_t*>(y), nullptr, B, H, W, 2 * H, 2 * W, Cin, 64,
-                SGX_ACT_NONE, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, static_cast<const unsigned char*>(maskbits)};
+    // the layer's geometry (the output is 2H x 2W) on the kernel's: a 3x3 convolution of the coarse grid to 64 = 4 parity classes x 16 channels
+    Conv2Args a = conv2_args(C2_U, x, wc, nullptr, y, B, H, W, Cin, 64, SGX_ACT_NONE);
+    a.maskbits = static_cast<const unsigned char*>(maskbits);
     a.wcorr = static_cast<const bf16_t*>(wc) + (size_t)9 * 64 * 32;
     // 8-wave blocks once their 512-pixel tiles fill the chip, else the 4-wave block (256-pixel tiles); SGX_UPBLUR_BPC=2: two compact 4-wave
     // blocks per CU (round 6)
-    static const int bpc2 = [] { const char* e = getenv("SGX_UPBLUR_BPC"); return e ? atoi(e) : 1; }();
     const long tiles8 = (long)B * ((H + 15) / 16) * (W / 32), tiles4 = (long)B * ((H + 7) / 8) * (W / 32);
-    if (bpc2 == 2 && tiles4 >= 2L * sgx_ncu()) return launch_conv3<C2_S, 4, 2, 2, 2, 0, 2>(a, (hipStream_t)stream);
+    if (upblur_bpc() == 2 && tiles4 >= 2L * sgx_ncu()) return launch_conv3<C2_S, 4, 2, 2, 2, 0, 2>(a, (hipStream_t)stream);
     return tiles8 >= sgx_ncu() ? launch_conv3<C2_S, 8, 2, 2, 2, 0, 1>(a, (hipStream_t)stream) : launch_conv3<C2_S, 4, 2, 2, 2, 0, 1>(a, (hipStream_t)stream);
 }
 
-// *launched = 1 if the second-generation kernel ran; 0 leaves the shape to the first-generation kernel.
-// would sgx_conv2_try (variant -1) take this bf16 shape?  (the split-K plan of conv.hip only covers launches that stay with the first generation)
+// The one map from a plan to the instantiation that runs it; every launcher of a Conv2Pick goes through here.  What exists: the
+// statistics epilogue for C2_S, the blur epilogue for C2_U (conv2_kernel's static_asserts), no 64-channel block for C2_U.  The
+// 16-channel forms: S 16->16 and U 32->16 store 16 of the block's 32 channels (U on full-width K-steps), D 16->32 is a whole block.
+template <int GEO, int EPI = EPI_NONE>
+static int conv2_run(const Conv2Pick& p, Conv2Args& a, hipStream_t st, bool plan_only = false) {
+    constexpr int KC16 = GEO == C2_U ? 32 : 16;
+    constexpr bool CO16 = GEO != C2_D;
+    const bool w8 = p.nw == 8;
+    if (p.k16) return w8 ? launch_conv2<GEO, 8, 1, KC16, CO16, EPI>(a, st, plan_only) : launch_conv2<GEO, 4, 1, KC16, CO16, EPI>(a, st, plan_only);
+    if constexpr (GEO != C2_U) {
+        if (p.mf2) return w8 ? launch_conv2<GEO, 8, 2, 32, false, EPI>(a, st, plan_only) : launch_conv2<GEO, 4, 2, 32, false, EPI>(a, st, plan_only);
+    }
+    return w8 ? launch_conv2<GEO, 8, 1, 32, false, EPI>(a, st, plan_only) : launch_conv2<GEO, 4, 1, 32, false, EPI>(a, st, plan_only);
+}
+
 int sgx_conv2_takes(int geo, int B, int H, int W, int Cin, int Cout) { return conv2_pick(geo, B, H, W, Cin, Cout, -1).nw != 0; }
 int sgx_conv2_try(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act,
                   const void* mask, int variant, hipStream_t st, int* launched) {
     *launched = 0;
+    Conv2Args a = conv2_args(geo, x, w, bias, y, B, H, W, Cin, Cout, act);
+    a.mask = static_cast<const bf16_t*>(mask);
     if (variant >= 30) {                          // conv3_kernel configurations (probes, tests): 30 + id of the table in conv3_variant
-        Conv2Args a3{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W,
-                     geo == C2_D ? H / 2 : H, geo == C2_D ? W / 2 : W, Cin, Cout, act, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-#ifdef SGX_PROBE_BUILD                            // DMA ablations (WRONG results by design): probe builds only (make PROBE=1)
-        { const char* e = getenv("SGX_CONV3_DBG"); a3.dbg = e ? atoi(e) : 0; }
+#ifdef SGX_PROBE_BUILD
+        a.dbg = conv3_dbg();
 #endif
-        const int rc = conv3_variant(geo, a3, variant - 30, st, launched);
-        return rc;
+        return conv3_variant(geo, a, variant - 30, st, launched);
     }
     if (variant == 20 || variant == 21) {        // probe: 128 output channels per block on 16-channel K-steps (one staged patch feeds 4 accumulator rows)
         if (geo != C2_S || Cin % 16 || Cout % 128 || W % 32) return 0;
-        Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W,
-                    H, W, Cin, Cout, act, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
         *launched = 1;
         return variant == 20 ? launch_conv2<C2_S, 8, 4, 16>(a, st) : launch_conv2<C2_S, 4, 4, 16>(a, st);
     }
+    Conv2Pick p;
     if (variant == 22 || variant == 23) {        // probe: 32 output channels per block (MF = 1) whatever Cout: twice the blocks of the 64-channel tile
         if ((geo != C2_S && geo != C2_D) || Cin % 32 || Cout % 32 || (geo == C2_D ? W / 2 : W) % 32) return 0;
-        Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W,
-                    geo == C2_D ? H / 2 : H, geo == C2_D ? W / 2 : W, Cin, Cout, act, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-        *launched = 1;
-        if (geo == C2_D) return variant == 22 ? launch_conv2<C2_D, 4, 1>(a, st) : launch_conv2<C2_D, 8, 1>(a, st);
-        return variant == 22 ? launch_conv2<C2_S, 4, 1>(a, st) : launch_conv2<C2_S, 8, 1>(a, st);
+        p = Conv2Pick{variant == 22 ? 4 : 8, false, false};
+    } else {
+        p = conv2_pick(geo, B, H, W, Cin, Cout, variant);
+        if (!p.nw) return 0;
     }
-    const Conv2Pick p = conv2_pick(geo, B, H, W, Cin, Cout, variant);
-    if (!p.nw) return 0;
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W,
-                geo == C2_D ? H / 2 : (geo == C2_U ? 2 * H : H), geo == C2_D ? W / 2 : (geo == C2_U ? 2 * W : W), Cin, Cout, act, 0, 0, 0, 0, 0, 0,
-                nullptr, nullptr, nullptr, nullptr, nullptr};
     *launched = 1;
-    const int nw = p.nw;
-    if (p.k16) {
-        if (geo == C2_S) return nw == 8 ? launch_conv2<C2_S, 8, 1, 16, true>(a, st) : launch_conv2<C2_S, 4, 1, 16, true>(a, st);
-        if (geo == C2_D) return nw == 8 ? launch_conv2<C2_D, 8, 1, 16, false>(a, st) : launch_conv2<C2_D, 4, 1, 16, false>(a, st);
-        return nw == 8 ? launch_conv2<C2_U, 8, 1, 32, true>(a, st) : launch_conv2<C2_U, 4, 1, 32, true>(a, st);
-    }
-    if (geo == C2_S) {
-        if (p.mf2) return nw == 8 ? launch_conv2<C2_S, 8, 2>(a, st) : launch_conv2<C2_S, 4, 2>(a, st);
-        return nw == 8 ? launch_conv2<C2_S, 8, 1>(a, st) : launch_conv2<C2_S, 4, 1>(a, st);
-    }
-    if (geo == C2_D) {
-        if (p.mf2) return nw == 8 ? launch_conv2<C2_D, 8, 2>(a, st) : launch_conv2<C2_D, 4, 2>(a, st);
-        return nw == 8 ? launch_conv2<C2_D, 8, 1>(a, st) : launch_conv2<C2_D, 4, 1>(a, st);
-    }
-    return nw == 8 ? launch_conv2<C2_U, 8, 1>(a, st) : launch_conv2<C2_U, 4, 1>(a, st);
+    return geo == C2_S ? conv2_run<C2_S>(p, a, st) : (geo == C2_D ? conv2_run<C2_D>(p, a, st) : conv2_run<C2_U>(p, a, st));
 }
 
 // ---- 3x3 convolution whose store also produces the instance-norm statistics of the LayerEpilogue that follows (generator
-// conv1 -> epi2, models/Blocks.py:86-87 over models/CustomLayers.py:224-233): tiles per image covered by the second-generation
-// kernel, 0 = this shape has no fused variant (the caller runs the plain convolution and the separate statistics pass).
-// tile slots of the persistent grid for a plan (== Conv2Args::nslots as launch_conv2 sets it)
-static int conv2_stats_slots(const Conv2Pick& p, int B, int H, int W, int Cout) {
-    const int th = 2 * p.nw, ntiles = B * ((H + th - 1) / th) * ((W + 31) / 32);
-    const int ncb = p.k16 ? 1 : Cout / (p.mf2 ? 64 : 32);
-    int bpc = 1;
-    if (p.k16) {
-        static const int bpc_max = [] { const char* e = getenv("SGX_CONV2_BPC"); return e ? atoi(e) : 2; }();
-        const int lds = (p.nw == 8 ? C2Lds<C2_S, 8, 1, 16>::TOTAL : C2Lds<C2_S, 4, 1, 16>::TOTAL) + 1024;
-        bpc = (160 * 1024) / lds;
-        if (bpc > 32 / p.nw) bpc = 32 / p.nw;
-        if (bpc > bpc_max) bpc = bpc_max;
-        if (bpc < 1) bpc = 1;
-    }
-    int per = conv2_ncu() * bpc / (8 * ncb);
-    const int need = (ntiles + 7) / 8;
-    if (per > need) per = need;
-    if (per < 1) per = 1;
-    return per * 8;
+// conv1 -> epi2, models/Blocks.py:86-87 over models/CustomLayers.py:224-233).  nparts: the tile slots of the launch's persistent grid
+// (Conv2Args::nslots, planned by the launcher itself), 0 = this shape has no fused variant (the caller runs the plain convolution and the
+// separate statistics pass).
+static int conv2_stats_slots(const Conv2Pick& p, int B, int H, int W, int Cin, int Cout) {
+    Conv2Args a = conv2_args(C2_S, nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Cout, SGX_ACT_NONE);
+    return conv2_run<C2_S, EPI_STATS>(p, a, nullptr, true) ? 0 : a.nslots;
 }
 extern "C" int sgx_conv3x3_stats_nparts(int B, int H, int W, int Cin, int Cout, int dtype) {
     if (dtype != SGX_BF16) return 0;
     const Conv2Pick p = conv2_pick(C2_S, B, H, W, Cin, Cout, -1);
-    if (!p.nw) return 0;
-    return conv2_stats_slots(p, B, H, W, Cout);
+    return p.nw ? conv2_stats_slots(p, B, H, W, Cin, Cout) : 0;
 }
 extern "C" int sgx_conv3x3_stats(const void* x, const void* w, void* y, const float* ebias, const float* noise, const float* nw_,
                                  double* part, size_t part_bytes, int B, int H, int W, int Cin, int Cout, int dtype, void* stream) {
@@ -1670,38 +1657,21 @@ extern "C" int sgx_conv3x3_stats(const void* x, const void* w, void* y, const fl
     SGX_REQUIRE(x && w && y && noise && nw_ && part, SGX_EINVAL, "conv3x3_stats: null argument");
     const Conv2Pick p = conv2_pick(C2_S, B, H, W, Cin, Cout, -1);
     SGX_REQUIRE(p.nw, SGX_EUNSUPPORTED, "conv3x3_stats: shape B%d %dx%d %d->%d has no fused variant (sgx_conv3x3_stats_nparts == 0)", B, H, W, Cin, Cout);
-    const int npart = conv2_stats_slots(p, B, H, W, Cout);
+    const int npart = conv2_stats_slots(p, B, H, W, Cin, Cout);
     SGX_REQUIRE(part_bytes >= (size_t)B * npart * Cout * 2 * sizeof(double), SGX_EWORKSPACE, "conv3x3_stats: partials buffer %zu < %zu", part_bytes,
                 (size_t)B * npart * Cout * 2 * sizeof(double));
     SGX_NOTE(2.0 * 9 * Cin * Cout * B * H * W, 2.0 * ((double)B * H * W * (Cin + Cout) + 9.0 * Cin * Cout), "convS+stats B%d %dx%d %d->%d", B, H, W, Cin, Cout);
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), nullptr, static_cast<bf16_t*>(y), nullptr, B, H, W, H, W, Cin, Cout,
-                SGX_ACT_NONE, 0, 0, 0, 0, 0, 0, ebias, noise, nw_, part, nullptr};
+    Conv2Args a = conv2_args(C2_S, x, w, nullptr, y, B, H, W, Cin, Cout, SGX_ACT_NONE);
+    a.ebias = ebias; a.enoise = noise; a.enw = nw_; a.part = part;
     a.part_slots = npart;
-    hipStream_t st = (hipStream_t)stream;
-    const int nw = p.nw;
-    if (p.k16) return nw == 8 ? launch_conv2<C2_S, 8, 1, 16, true, EPI_STATS>(a, st) : launch_conv2<C2_S, 4, 1, 16, true, EPI_STATS>(a, st);
-    if (p.mf2) return nw == 8 ? launch_conv2<C2_S, 8, 2, 32, false, EPI_STATS>(a, st) : launch_conv2<C2_S, 4, 2, 32, false, EPI_STATS>(a, st);
-    return nw == 8 ? launch_conv2<C2_S, 8, 1, 32, false, EPI_STATS>(a, st) : launch_conv2<C2_S, 4, 1, 32, false, EPI_STATS>(a, st);
+    return conv2_run<C2_S, EPI_STATS>(p, a, (hipStream_t)stream);
 }
 
 // ---- transposed convolution + the blur that follows it (+ the LeakyReLU-backward mask of the discriminator's backward chain)
 // in one kernel: 1 if this shape has the fused variant, 0 = the caller runs sgx_conv4x4s2_up and sgx_blur3x3(_act).
 extern "C" int sgx_conv4x4s2_up_blur_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
-    if (dtype != SGX_BF16) return 0;
-    static const int on = [] { const char* e = getenv("SGX_CONV_UP_BLUR"); return e ? atoi(e) : 1; }();   // A/B switch
-    if (!on) return 0;
+    if (dtype != SGX_BF16 || !conv_up_blur_on()) return 0;
     return conv2_pick(C2_U, B, H, W, Cin, Cout, -1, true).nw ? 1 : 0;
-}
-static int conv_up_blur_launch(const void* x, const void* w, void* y, const void* mask, const void* maskbits, int B, int H, int W, int Cin, int Cout,
-                               int dtype, void* stream);
-extern "C" int sgx_conv4x4s2_up_blur(const void* x, const void* w, void* y, const void* mask, int B, int H, int W, int Cin, int Cout,
-                                     int dtype, void* stream) {
-    return conv_up_blur_launch(x, w, y, mask, nullptr, B, H, W, Cin, Cout, dtype, stream);
-}
-extern "C" int sgx_conv4x4s2_up_blur_bits(const void* x, const void* w, void* y, const void* bits, int B, int H, int W, int Cin, int Cout,
-                                          int dtype, void* stream) {
-    SGX_REQUIRE(bits && Cout % 8 == 0, SGX_EINVAL, "conv4x4s2_up_blur_bits: sign bits [B][2H][2W][Cout/8] expected");
-    return conv_up_blur_launch(x, w, y, nullptr, bits, B, H, W, Cin, Cout, dtype, stream);
 }
 static int conv_up_blur_launch(const void* x, const void* w, void* y, const void* mask, const void* maskbits, int B, int H, int W, int Cin, int Cout,
                                int dtype, void* stream) {
@@ -1711,11 +1681,19 @@ static int conv_up_blur_launch(const void* x, const void* w, void* y, const void
     SGX_REQUIRE(p.nw, SGX_EUNSUPPORTED, "conv4x4s2_up_blur: shape B%d %dx%d %d->%d has no fused variant (sgx_conv4x4s2_up_blur_ok == 0)", B, H, W, Cin, Cout);
     SGX_NOTE(2.0 * 16 * Cin * Cout * B * H * W, 2.0 * ((double)B * H * W * (Cin + 4.0 * Cout * (mask ? 2 : 1)) + 16.0 * Cin * Cout) + (maskbits ? 0.5 * B * H * W * Cout : 0.0),
              "convU+blur%s B%d %dx%d %d->%d", mask ? "*mask" : (maskbits ? "*bits" : ""), B, H, W, Cin, Cout);
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), nullptr, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W,
-                2 * H, 2 * W, Cin, Cout, SGX_ACT_NONE, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, static_cast<const unsigned char*>(maskbits)};
-    hipStream_t st = (hipStream_t)stream;
-    if (p.k16) return p.nw == 8 ? launch_conv2<C2_U, 8, 1, 32, true, EPI_BLUR>(a, st) : launch_conv2<C2_U, 4, 1, 32, true, EPI_BLUR>(a, st);
-    return p.nw == 8 ? launch_conv2<C2_U, 8, 1, 32, false, EPI_BLUR>(a, st) : launch_conv2<C2_U, 4, 1, 32, false, EPI_BLUR>(a, st);
+    Conv2Args a = conv2_args(C2_U, x, w, nullptr, y, B, H, W, Cin, Cout, SGX_ACT_NONE);
+    a.mask = static_cast<const bf16_t*>(mask);
+    a.maskbits = static_cast<const unsigned char*>(maskbits);
+    return conv2_run<C2_U, EPI_BLUR>(p, a, (hipStream_t)stream);
+}
+extern "C" int sgx_conv4x4s2_up_blur(const void* x, const void* w, void* y, const void* mask, int B, int H, int W, int Cin, int Cout,
+                                     int dtype, void* stream) {
+    return conv_up_blur_launch(x, w, y, mask, nullptr, B, H, W, Cin, Cout, dtype, stream);
+}
+extern "C" int sgx_conv4x4s2_up_blur_bits(const void* x, const void* w, void* y, const void* bits, int B, int H, int W, int Cin, int Cout,
+                                          int dtype, void* stream) {
+    SGX_REQUIRE(bits && Cout % 8 == 0, SGX_EINVAL, "conv4x4s2_up_blur_bits: sign bits [B][2H][2W][Cout/8] expected");
+    return conv_up_blur_launch(x, w, y, nullptr, bits, B, H, W, Cin, Cout, dtype, stream);
 }
 
 // ---- 3x3 convolution that also writes the SIGN bits of its (bias-added, activated) output: one byte per pixel and 8 channels.
@@ -1723,8 +1701,7 @@ static int conv_up_blur_launch(const void* x, const void* w, void* y, const void
 // backward passes then read 1 bit instead of 16 per element.  1 = available for this shape (bf16, second-generation kernel).
 extern "C" int sgx_conv3x3_signbits_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
     if (dtype != SGX_BF16 || Cout % 8) return 0;
-    static const int on = [] { const char* e = getenv("SGX_SIGNBITS"); return e ? atoi(e) : 1; }();   // A/B switch
-    return on && conv2_pick(C2_S, B, H, W, Cin, Cout, -1).nw ? 1 : 0;
+    return signbits_on() && conv2_pick(C2_S, B, H, W, Cin, Cout, -1).nw ? 1 : 0;
 }
 extern "C" int sgx_conv3x3_signbits(const void* x, const void* w, const float* bias, void* y, void* bits, int B, int H, int W, int Cin,
                                     int Cout, int act, const void* mask, int dtype, void* stream) {
@@ -1734,29 +1711,39 @@ extern "C" int sgx_conv3x3_signbits(const void* x, const void* w, const float* b
     SGX_REQUIRE(p.nw && Cout % 8 == 0, SGX_EUNSUPPORTED, "conv3x3_signbits: shape B%d %dx%d %d->%d has no variant (sgx_conv3x3_signbits_ok == 0)", B, H, W, Cin, Cout);
     SGX_NOTE(2.0 * 9 * Cin * Cout * B * H * W, 2.0 * ((double)B * H * W * (Cin + Cout) + 9.0 * Cin * Cout) + (double)B * H * W * Cout / 8.0,
              "convS+bits B%d %dx%d %d->%d", B, H, W, Cin, Cout);
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), static_cast<const bf16_t*>(mask), B, H, W, H, W,
-                Cin, Cout, act, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, static_cast<unsigned char*>(bits)};
-    hipStream_t st = (hipStream_t)stream;
-    const int nw = p.nw;
-    if (p.k16) return nw == 8 ? launch_conv2<C2_S, 8, 1, 16, true>(a, st) : launch_conv2<C2_S, 4, 1, 16, true>(a, st);
-    if (p.mf2) return nw == 8 ? launch_conv2<C2_S, 8, 2>(a, st) : launch_conv2<C2_S, 4, 2>(a, st);
-    return nw == 8 ? launch_conv2<C2_S, 8, 1>(a, st) : launch_conv2<C2_S, 4, 1>(a, st);
+    Conv2Args a = conv2_args(C2_S, x, w, bias, y, B, H, W, Cin, Cout, act);
+    a.mask = static_cast<const bf16_t*>(mask);
+    a.signbits = static_cast<unsigned char*>(bits);
+    return conv2_run<C2_S>(p, a, (hipStream_t)stream);
 }
 
 // ---- stride-2 convolution whose store applies the fade-in lerp of the discriminator's newest block and writes the activation's sign
 // bits instead of the activation (models/GAN.py:425-427 over models/Blocks.py:143-146):  y = alpha * lrelu(conv(x) + bias) + beta * resid.
 extern "C" int sgx_conv4x4s2_down_fade_ok(int B, int H, int W, int Cin, int Cout, int dtype) {
     if (dtype != SGX_BF16 || Cout % 8) return 0;
-    static const int on = [] { const char* e = getenv("SGX_FUSE_FADE"); return e ? atoi(e) : 1; }();   // A/B switch
-    return on && conv2_pick(C2_D, B, H, W, Cin, Cout, -1).nw ? 1 : 0;
+    return fuse_fade_on() && conv2_pick(C2_D, B, H, W, Cin, Cout, -1).nw ? 1 : 0;
 }
-static int conv_down_fade_launch(const void* x, const void* w, const float* bias, const void* resid, const float* pimg, const float* wr, const float* rb,
-                                 float ws, float bs1, float bs2, float alpha, float beta, const float* ab_dev, void* y, void* bits, int B, int H, int W, int Cin,
-                                 int Cout, int dtype, void* stream);
+// the two entry points below; `a`: x, w, bias, y, the shape and the residual's members set
+static int conv_down_fade_launch(Conv2Args& a, float alpha, float beta, const float* ab_dev, void* bits, int dtype, void* stream) {
+    const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
+    SGX_REQUIRE(dtype == SGX_BF16, SGX_EUNSUPPORTED, "conv4x4s2_down_fade: bf16 only");
+    SGX_REQUIRE(a.x && a.w && a.y && bits, SGX_EINVAL, "conv4x4s2_down_fade: null argument");
+    const Conv2Pick p = conv2_pick(C2_D, B, H, W, Cin, Cout, -1);
+    SGX_REQUIRE(p.nw && Cout % 8 == 0, SGX_EUNSUPPORTED, "conv4x4s2_down_fade: shape B%d %dx%d %d->%d has no variant (sgx_conv4x4s2_down_fade_ok == 0)", B, H, W, Cin, Cout);
+    const bool rgb = a.fade_pimg != nullptr;
+    const double opx = (double)B * (H / 2) * (W / 2);
+    SGX_NOTE(2.0 * 16 * Cin * Cout * opx, 2.0 * ((double)B * H * W * Cin + (rgb ? 1.0 : 2.0) * opx * Cout + 16.0 * Cin * Cout) + opx * Cout / 8.0 + (rgb ? 12.0 * opx : 0.0),
+             "convD+fade%s B%d %dx%d %d->%d", rgb ? "(rgb)" : "", B, H, W, Cin, Cout);
+    a.signbits = static_cast<unsigned char*>(bits);
+    a.fade_alpha = alpha; a.fade_beta = beta; a.fade_ab = ab_dev;
+    return conv2_run<C2_D>(p, a, (hipStream_t)stream);
+}
 extern "C" int sgx_conv4x4s2_down_fade(const void* x, const void* w, const float* bias, const void* resid, float alpha, float beta, const float* ab_dev,
                                        void* y, void* bits, int B, int H, int W, int Cin, int Cout, int dtype, void* stream) {
     SGX_REQUIRE(resid, SGX_EINVAL, "conv4x4s2_down_fade: null argument");
-    return conv_down_fade_launch(x, w, bias, resid, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, alpha, beta, ab_dev, y, bits, B, H, W, Cin, Cout, dtype, stream);
+    Conv2Args a = conv2_args(C2_D, x, w, bias, y, B, H, W, Cin, Cout, SGX_ACT_LRELU);
+    a.fade_resid = static_cast<const bf16_t*>(resid);
+    return conv_down_fade_launch(a, alpha, beta, ab_dev, bits, dtype, stream);
 }
 // ... with the residual branch from_rgb(pimg) computed in the store: pimg fp32 [B][H/2][W/2][3] (the down-sampled image), wr = from_rgb.weight
 // [Cout][3][1][1], ws = its w_mul (x the prescale of the residual, if any), rb = from_rgb.bias or NULL with its two scales (b_mul, prescale)
@@ -1764,24 +1751,7 @@ extern "C" int sgx_conv4x4s2_down_fade_rgb(const void* x, const void* w, const f
                                            float bs1, float bs2, float alpha, float beta, const float* ab_dev, void* y, void* bits, int B, int H, int W,
                                            int Cin, int Cout, int dtype, void* stream) {
     SGX_REQUIRE(pimg && wr, SGX_EINVAL, "conv4x4s2_down_fade_rgb: null argument");
-    return conv_down_fade_launch(x, w, bias, nullptr, pimg, wr, rb, ws, bs1, bs2, alpha, beta, ab_dev, y, bits, B, H, W, Cin, Cout, dtype, stream);
-}
-static int conv_down_fade_launch(const void* x, const void* w, const float* bias, const void* resid, const float* pimg, const float* wr, const float* rb,
-                                 float ws, float bs1, float bs2, float alpha, float beta, const float* ab_dev, void* y, void* bits, int B, int H, int W, int Cin,
-                                 int Cout, int dtype, void* stream) {
-    SGX_REQUIRE(dtype == SGX_BF16, SGX_EUNSUPPORTED, "conv4x4s2_down_fade: bf16 only");
-    SGX_REQUIRE(x && w && y && bits, SGX_EINVAL, "conv4x4s2_down_fade: null argument");
-    const Conv2Pick p = conv2_pick(C2_D, B, H, W, Cin, Cout, -1);
-    SGX_REQUIRE(p.nw && Cout % 8 == 0, SGX_EUNSUPPORTED, "conv4x4s2_down_fade: shape B%d %dx%d %d->%d has no variant (sgx_conv4x4s2_down_fade_ok == 0)", B, H, W, Cin, Cout);
-    const double opx = (double)B * (H / 2) * (W / 2);
-    SGX_NOTE(2.0 * 16 * Cin * Cout * opx, 2.0 * ((double)B * H * W * Cin + (pimg ? 1.0 : 2.0) * opx * Cout + 16.0 * Cin * Cout) + opx * Cout / 8.0 + (pimg ? 12.0 * opx : 0.0),
-             "convD+fade%s B%d %dx%d %d->%d", pimg ? "(rgb)" : "", B, H, W, Cin, Cout);
-    Conv2Args a{static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), bias, static_cast<bf16_t*>(y), nullptr, B, H, W, H / 2, W / 2, Cin, Cout,
-                SGX_ACT_LRELU, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, static_cast<unsigned char*>(bits), nullptr,
-                static_cast<const bf16_t*>(resid), alpha, beta, ab_dev, pimg, wr, rb, ws, bs1, bs2};
-    hipStream_t st = (hipStream_t)stream;
-    const int nw = p.nw;
-    if (p.k16) return nw == 8 ? launch_conv2<C2_D, 8, 1, 16, false>(a, st) : launch_conv2<C2_D, 4, 1, 16, false>(a, st);
-    if (p.mf2) return nw == 8 ? launch_conv2<C2_D, 8, 2>(a, st) : launch_conv2<C2_D, 4, 2>(a, st);
-    return nw == 8 ? launch_conv2<C2_D, 8, 1>(a, st) : launch_conv2<C2_D, 4, 1>(a, st);
+    Conv2Args a = conv2_args(C2_D, x, w, bias, y, B, H, W, Cin, Cout, SGX_ACT_LRELU);
+    a.fade_pimg = pimg; a.fade_wr = wr; a.fade_rb = rb; a.fade_ws = ws; a.fade_bs1 = bs1; a.fade_bs2 = bs2;
+    return conv_down_fade_launch(a, alpha, beta, ab_dev, bits, dtype, stream);
 }
