@@ -128,6 +128,13 @@ int sgx_pack_weight_multi(const void* table, int n, int total_blocks, int dtype,
  *                        D on real and fake images, the R1 double backward -- accumulates in the finishing kernel
  *                        instead of a separate add per contribution).                                               */
 size_t sgx_wgrad_ws_bytes(int taps, int B, int H, int W, int Ck, int Cn);
+/* Host-only query: what a weight-gradient call of this shape and workspace will launch (taps 9: sgx_wgrad3x3_param, 16: sgx_wgrad4x4s2_param; H, W, Ck = Cx /
+ * Cfine, Cn = Cdy / Ccoarse as those take them).  The launchers run the same plan.  out[SGX_WGRAD_PLAN_INTS] = {generation 1 / 2; TH, TW, BP, NSUB, KSUB, TR:
+ * the template arguments of wgrad_kernel<T, geo, ...> as rocprofv3 prints them (generation 2: the pixel tile TH x TW = BP, NSUB 0, KSUB = the kernel's KBW,
+ * 16 for wgrad16_s_kernel); pixel splits; the splits the finishing launch reads (0: no finishing launch, the gradient kernel writes dW / db itself);
+ * pre-reduction 0 / 1; the finishing kernel's EPB}.  Returns the call's error code: 0, SGX_EUNSUPPORTED, SGX_EWORKSPACE. */
+#define SGX_WGRAD_PLAN_INTS 11
+int sgx_wgrad_plan(int taps, int B, int H, int W, int Ck, int Cn, int dtype, size_t ws_bytes, int* out);
 int sgx_wgrad3x3_param(const void* x, const void* dy, float* dW, float* db, void* ws, size_t ws_bytes, int B, int H, int W,
                        int Cx, int Cdy, int adjoint, float scale, int O, int I, int accumulate, int dtype, void* stream);
 int sgx_wgrad4x4s2_param(const void* fine, const void* coarse, float* dW, float* db, void* ws, size_t ws_bytes, int B, int H,

@@ -147,11 +147,13 @@ static inline int sgx_conv_out(int geo, int n) { return geo == 1 ? n / 2 : (geo 
 int sgx_conv2_try(int geo, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int act,
                   const void* mask, int variant, hipStream_t st, int* launched);
 int sgx_conv2_takes(int geo, int B, int H, int W, int Cin, int Cout);
-// wgrad2.hip, the second-generation bf16 weight gradients, for conv.hip: plan = pixel splits (0: the shape stays with wgrad_kernel); launch
+// wgrad2.hip, the second-generation bf16 weight gradients, for conv.hip (H, W = the n side's size).  plan: ns = pixel splits (0: the shape
+// stays with wgrad_kernel), channel tiles, KBW (16: wgrad16_s_kernel), the th x tw pixel tiles of the n-side grid; launch runs that plan and
 // writes the same per-split partials as wgrad_kernel
-int sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn, int* nct_n, int* nct_k, int* kbw, int* ntiles);
-int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, size_t ws_bytes, int B, int H, int W, int Ck, int Cn,
-                      int want_bias, hipStream_t st, int* nsplit_out);
+struct Wg2Plan { int ns, nct_n, nct_k, kbw, ntiles, th, tw, tiles_x, tiles_y; };
+Wg2Plan sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn);
+int sgx_wgrad2_launch(int geo, const Wg2Plan& p, const void* kside, const void* nside, float* ws, int B, int H, int W, int Ck, int Cn,
+                      int want_bias, hipStream_t st);
 
 // ---- per-launch profiler (sgx_prof_* in include/sgx.h) --------------------------------------
 // Every kernel launch of the library goes through sgx_launch.  When profiling is on it is bracketed by two HIP events

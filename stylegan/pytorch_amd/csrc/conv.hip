@@ -1215,16 +1215,24 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(FinishArgs f) {
     }
 }
 
+// ---- the launch layer.  What one call does is decided once, by wgrad_plan, for the entry points, sgx_wgrad_plan and (through the same
+// helpers) sgx_wgrad_ws_bytes.  Switches; the three block / split targets treat a value <= 0 as unset.
+SGX_SWITCH(wgrad_blocks_env, "SGX_WGRAD_BLOCKS", 0)
+SGX_SWITCH(wgrad_maxsplit_env, "SGX_WGRAD_MAXSPLIT", 0)
+SGX_SWITCH(wgrad_blocks_mid_env, "SGX_WGRAD_BLOCKS_MID", 0)
+SGX_SWITCH(wgrad_tr_on, "SGX_WGRAD_TR", 1)                 // 0 / 1: the plain / transpose-read bf16 operand path (A/B for parity tests and profiling)
+SGX_SWITCH(wgrad_pre_groups, "SGX_WGRAD_PRE", 32)          // groups of the pre-reduction; 0 switches the pass off (A/B)
+SGX_SWITCH(wgrad_pre_min, "SGX_WGRAD_PRE_MIN", 256)
+
 // Pixel splits per channel pair.  ~512 blocks for the mid layers (measured 18.20 -> 18.05 ms/step against 1024: half the
-// partial traffic); the 16/32-channel layers at 512^2..1024^2 (a handful of
-// channel pairs, millions of pixels, partials of a few KB per split) take 2048 blocks / up to 1024 splits -- measured:
+// partial traffic); the 16/32-channel layers at 512^2..1024^2 (a handful of channel pairs, millions of pixels, partials
+// of a few KB per split) take 2048 blocks / up to 1024 splits -- measured:
 // 118 -> 87 us for the 1024^2 16x16 layer -- while for bigger weights more splits cost more in partial traffic than they
 // gain (measured).  SGX_WGRAD_BLOCKS / SGX_WGRAD_MAXSPLIT override both for experiments.
 static int wgrad_nsplit(int pairs, int ntiles, size_t elems_per_split) {
-    static const int env_target = [] { const char* e = getenv("SGX_WGRAD_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-    static const int env_cap = [] { const char* e = getenv("SGX_WGRAD_MAXSPLIT"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
+    const int env_target = wgrad_blocks_env() > 0 ? wgrad_blocks_env() : 0, env_cap = wgrad_maxsplit_env() > 0 ? wgrad_maxsplit_env() : 0;
+    const int env_mid = wgrad_blocks_mid_env() > 0 ? wgrad_blocks_mid_env() : 0;
     const bool tiny = elems_per_split <= (size_t)16 * 32 * 32;
-    static const int env_mid = [] { const char* e = getenv("SGX_WGRAD_BLOCKS_MID"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
     const int target = env_target ? env_target : (tiny ? 2048 : (env_mid ? env_mid : 512)), cap = env_cap ? env_cap : (tiny ? 1024 : 512);
     int want = (target + pairs - 1) / pairs;
     // big weights at low resolution (512x512 channels at 4^2..32^2): with >= 512 channel pairs the grid is full without
@@ -1237,67 +1245,9 @@ static int wgrad_nsplit(int pairs, int ntiles, size_t elems_per_split) {
     return want;
 }
 
-template <typename T, int GEO, int TH, int TW, int BP, int NSUB, int KSUB, bool TR>
-static int launch_wgrad(WgradArgs& a, void* ws, size_t ws_bytes, int* nsplit_out, hipStream_t st) {
-    using F = WFrag<T>;
-    constexpr int IS = Geo<GEO>::IS, TK = Geo<GEO>::TK, NT = TK * TK;
-    constexpr int PH = (TH - 1) * IS + TK, PW = (TW - 1) * IS + TK, NI = BP / (TH * TW);
-    constexpr int OPER = BP * wgrad_pitch<T>(NSUB * 16, TR, 1) + NI * PH * PW * wgrad_pitch<T>(KSUB * 16, TR, IS);
-    constexpr int FOLD = NT * NSUB * 16 * (KSUB * 16 + 1) * 4;          // direct epilogue: all taps of the tile, fp32
-    constexpr int LDS = OPER > FOLD ? OPER : FOLD;
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    a.tiles_y = (a.Hn + TH - 1) / TH; a.tiles_x = (a.Wn + TW - 1) / TW;
-    a.ntiles = ((a.B + NI - 1) / NI) * a.tiles_y * a.tiles_x;
-    const int pairs = (a.Cn / (NSUB * 16)) * (a.Ck / (KSUB * 16));
-    int nsplit = wgrad_nsplit(pairs, a.ntiles, (size_t)NT * a.Cn * a.Ck);
-    const size_t total = (size_t)NT * a.Cn * a.Ck + a.Cn;             // per split: all taps + the n side's column sums
-    size_t fit = ws_bytes / (total * sizeof(float));
-    if ((size_t)nsplit > fit) nsplit = (int)fit;
-    SGX_REQUIRE(nsplit >= 1, SGX_EWORKSPACE, "wgrad: workspace too small (%zu bytes, need >= %zu)", ws_bytes, total * sizeof(float));
-    a.out = static_cast<float*>(ws);
-    a.direct = (nsplit == 1 && a.dw != nullptr) ? 1 : 0;
-    auto kern = wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR>;
-    sgx_lds_opt_in<wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR>>(LDS);
-    hipLaunchKernelGGL(kern, dim3(pairs, nsplit), dim3(256), LDS, st, a);
-    SGX_LAUNCH_CHECK("wgrad_kernel");
-    *nsplit_out = nsplit;
-    return 0;
-}
-
-template <typename T, int GEO, int BP, int NSUB, int KSUB, bool TR>
-static int wgrad_tile(WgradArgs& a, void* ws, size_t wsb, int* ns, hipStream_t st) {
-    if (a.Hn >= 16 && a.Wn >= 16) return launch_wgrad<T, GEO, BP / 16, 16, BP, NSUB, KSUB, TR>(a, ws, wsb, ns, st);
-    if (a.Hn >= 8 && a.Wn >= 8) return launch_wgrad<T, GEO, (BP >= 64 ? 8 : BP / 8), 8, BP, NSUB, KSUB, TR>(a, ws, wsb, ns, st);
-    return launch_wgrad<T, GEO, (BP >= 16 ? 4 : BP / 4), 4, BP, NSUB, KSUB, TR>(a, ws, wsb, ns, st);
-}
-
-// SGX_WGRAD_TR=0/1 selects the plain / transpose-read bf16 operand path (A/B switch for parity tests and profiling)
-static bool wgrad_use_tr() {
-    static const int v = [] { const char* e = getenv("SGX_WGRAD_TR"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
-
-template <typename T, int GEO, int BP, bool TR = false>
-static int wgrad_ch(WgradArgs& a, void* ws, size_t wsb, int* ns, hipStream_t st) {
-    SGX_REQUIRE(a.Cn % 16 == 0 && a.Ck % 16 == 0, SGX_EUNSUPPORTED, "wgrad: channels must be multiples of 16");
-    const bool n32 = a.Cn % 32 == 0, k32 = a.Ck % 32 == 0;
-    if (GEO == GDOWN) {                                       // fine patch is 4x larger: keep the k side at 16 channels
-        if (n32) return wgrad_tile<T, GEO, BP, 2, 1, TR>(a, ws, wsb, ns, st);
-        return wgrad_tile<T, GEO, BP, 1, 1, TR>(a, ws, wsb, ns, st);
-    }
-    const long npix = (long)a.B * a.Hn * a.Wn;
-    const bool lowres_big = npix <= 64L * BP && (long)(a.Cn / 32) * (a.Ck / 32) < 512 && (long)(a.Cn / 32) * (a.Ck / 16) >= 512;
-    if (n32 && k32 && !lowres_big) return wgrad_tile<T, GEO, BP, 2, 2, TR>(a, ws, wsb, ns, st);
-    if (n32) return wgrad_tile<T, GEO, BP, 2, 1, TR>(a, ws, wsb, ns, st);
-    if (k32) return wgrad_tile<T, GEO, BP, 1, 2, TR>(a, ws, wsb, ns, st);
-    return wgrad_tile<T, GEO, BP, 1, 1, TR>(a, ws, wsb, ns, st);
-}
-
 // Pre-reduction for the many-split case (tiny weights at 512^2..1024^2: 256..1024 splits of a few KB): groups of splits are
 // summed element-wise with fully coalesced 16-byte loads into 32 groups, which the finishing kernel then treats as
 // its splits.  (The finishing kernel alone reads a 16..32-byte run per split: 70 us for 38 MB of partials.)
-static int wgrad_pre_groups() { static const int v = [] { const char* e = getenv("SGX_WGRAD_PRE"); return e ? atoi(e) : 32; }(); return v; }
-static int wgrad_pre_min() { static const int v = [] { const char* e = getenv("SGX_WGRAD_PRE_MIN"); return e ? atoi(e) : 256; }(); return v; }
 __global__ __launch_bounds__(256) void wgrad_prereduce_kernel(const float* __restrict__ ws, float* __restrict__ out, size_t total4,
                                                               int nsplit) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;      // float4 index inside one split
@@ -1313,76 +1263,171 @@ __global__ __launch_bounds__(256) void wgrad_prereduce_kernel(const float* __res
     reinterpret_cast<float4*>(out)[(size_t)g * total4 + e] = acc;
 }
 static size_t wgrad_pre_bytes(size_t total_floats, int nsplit) {
-    const int G = wgrad_pre_groups();                                  // SGX_WGRAD_PRE=0 switches the pass off (A/B)
+    const int G = wgrad_pre_groups();
     return (G > 0 && nsplit >= wgrad_pre_min() && nsplit > G && total_floats % 4 == 0) ? (size_t)G * total_floats * sizeof(float) : 0;
 }
+// the finishing kernel's EPB: the widest contiguous run per split lane (coalescing: the partials are read once per split) that
+// still leaves >= 128 blocks
+static int wgrad_finish_epb(int ne) { return ne / 64 >= 128 ? 64 : (ne / 16 >= 128 ? 16 : (ne / 8 >= 128 ? 8 : 4)); }
 
-static int wgrad_finish(const void* ws, float* dw, float* db, int nsplit, int O, int I, int Ip, int mode, int transposed, int flip_t,
-                        float scale, int accumulate, hipStream_t st, size_t ws_bytes = 0) {
-    {
-        const size_t total = (size_t)(mode == SGX_PACK_S ? 9 : 16) * O * Ip + (transposed ? Ip : O);
-        const size_t pre = wgrad_pre_bytes(total, nsplit), used = (size_t)nsplit * total * sizeof(float);
-        if (pre && ws_bytes >= used + pre) {
-            float* out = reinterpret_cast<float*>(const_cast<char*>(static_cast<const char*>(ws)) + used);
-            hipLaunchKernelGGL(wgrad_prereduce_kernel, dim3((unsigned)((total / 4 + 255) / 256), wgrad_pre_groups()), dim3(256), 0, st,
-                               static_cast<const float*>(ws), out, total / 4, nsplit);
-            SGX_LAUNCH_CHECK("wgrad_prereduce_kernel");
-            ws = out;
-            nsplit = wgrad_pre_groups();
+// Everything one call will do.  Generation 1 is wgrad_kernel<T, geo, th, tw, bp, nsub, ksub, tr> on a grid of pairs x nsplit; generation 2
+// (bf16, wgrad2.hip) is g2, with th x tw = bp its pixel tile and ksub its KBW.
+struct WgradPlan {
+    int rc, gen, th, tw, bp, nsub, ksub, tr;   // rc: 0, SGX_EUNSUPPORTED or SGX_EWORKSPACE (the message is set)
+    int tiles_x, tiles_y, ntiles, pairs;       // generation 1: the n-side grid in tiles of bp pixels, the channel pairs
+    int nsplit, direct;                        // pixel splits after the workspace clamp; direct: the block writes dW / db itself
+    int pre, finish_ns, epb;                   // the pre-reduction runs; the finishing launch's splits (0: direct) and elements per block
+    size_t total, used;                        // floats per split: all taps + the n side's column sums; workspace bytes the call writes
+    Wg2Plan g2;
+};
+// KSUB, the k side's 16-channel sub-tiles of a block (NSUB, the n side's: 2 where Cn % 32 == 0).  Stride 2: the fine patch is 4x
+// larger, one sub-tile
+static int wgrad_ch(int geo, int bp, long npix, int Ck, int Cn) {
+    // 512 x 512 channels on a few pixels: (2, 1) gives the >= 512 channel pairs of the one-split rule of wgrad_nsplit
+    const bool lowres_big = npix <= 64L * bp && (long)(Cn / 32) * (Ck / 32) < 512 && (long)(Cn / 32) * (Ck / 16) >= 512;
+    return geo == GDOWN || Ck % 32 || (Cn % 32 == 0 && lowres_big) ? 1 : 2;
+}
+// TW of the pixel tile: bp / 16 x 16, 8 x 8 or 4 x 4
+static int wgrad_tile(int Hn, int Wn) { return Hn >= 16 && Wn >= 16 ? 16 : (Hn >= 8 && Wn >= 8 ? 8 : 4); }
+static WgradPlan wgrad_plan(int geo, int dtype, int B, int Hn, int Wn, int Ck, int Cn, size_t ws_bytes) {
+    WgradPlan p{};
+    const int NT = geo == G3X3 ? 9 : 16;
+    p.total = (size_t)NT * Cn * Ck + Cn; p.epb = wgrad_finish_epb(Ck * Cn);
+    if (dtype == SGX_BF16) p.g2 = sgx_wgrad2_plan(geo, B, Hn, Wn, Ck, Cn);
+    if (p.g2.ns && (size_t)p.g2.ns * p.total * sizeof(float) <= ws_bytes) {   // (a workspace too small for its splits: the first generation)
+        p.gen = 2; p.th = p.g2.th; p.tw = p.g2.tw; p.bp = p.th * p.tw; p.ksub = p.g2.kbw; p.ntiles = p.g2.ntiles; p.nsplit = p.g2.ns;
+    } else {
+        p.gen = 1; p.bp = geo == G3X3 ? 128 : 64; p.tr = dtype == SGX_BF16 && wgrad_tr_on() != 0;
+        if (Cn % 16 || Ck % 16) { sgx_set_error("wgrad: channels must be multiples of 16"); p.rc = SGX_EUNSUPPORTED; return p; }
+        p.nsub = Cn % 32 ? 1 : 2; p.ksub = wgrad_ch(geo, p.bp, (long)B * Hn * Wn, Ck, Cn);
+        p.tw = wgrad_tile(Hn, Wn); p.th = p.tw == 16 ? p.bp / 16 : p.tw;
+        const int ni = p.bp / (p.th * p.tw);                               // images per block
+        p.tiles_y = (Hn + p.th - 1) / p.th; p.tiles_x = (Wn + p.tw - 1) / p.tw;
+        p.ntiles = ((B + ni - 1) / ni) * p.tiles_y * p.tiles_x;
+        p.pairs = (Cn / (p.nsub * 16)) * (Ck / (p.ksub * 16));
+        p.nsplit = wgrad_nsplit(p.pairs, p.ntiles, (size_t)NT * Cn * Ck);
+        const size_t fit = ws_bytes / (p.total * sizeof(float));
+        if ((size_t)p.nsplit > fit) p.nsplit = (int)fit;
+        if (p.nsplit < 1) {
+            sgx_set_error("wgrad: workspace too small (%zu bytes, need >= %zu)", ws_bytes, p.total * sizeof(float));
+            p.rc = SGX_EWORKSPACE;
+            return p;
         }
+        p.direct = p.nsplit == 1;                  // (dW is never NULL: the finishing kernel writes it unconditionally too)
     }
-    FinishArgs f{static_cast<const float*>(ws), dw, db, nsplit, O, I, Ip, mode, transposed, flip_t, scale, accumulate};
-    SGX_NOTE(0.0, 4.0 * ((double)nsplit * (mode == SGX_PACK_S ? 9 : 16) * O * Ip + 9.0 * O * I), "finish %dx%d m%d tr%d ns%d", O, I, mode, transposed, nsplit);
-    const int ne = O * Ip, nb = db ? O : 0;                            // bias blocks trail the weight blocks
-    // widest contiguous run per split lane (coalescing: the partials are read once per split) that still leaves >= 128 blocks
-    if (ne / 64 >= 128) hipLaunchKernelGGL(wgrad_finish_kernel<64>, dim3((unsigned)((ne + 63) / 64 + (nb + 63) / 64)), dim3(256), 0, st, f);
-    else if (ne / 16 >= 128) hipLaunchKernelGGL(wgrad_finish_kernel<16>, dim3((unsigned)((ne + 15) / 16 + (nb + 15) / 16)), dim3(256), 0, st, f);
-    else if (ne / 8 >= 128) hipLaunchKernelGGL(wgrad_finish_kernel<8>, dim3((unsigned)((ne + 7) / 8 + (nb + 7) / 8)), dim3(256), 0, st, f);
-    else hipLaunchKernelGGL(wgrad_finish_kernel<4>, dim3((unsigned)((ne + 3) / 4 + (nb + 3) / 4)), dim3(256), 0, st, f);
+    p.used = (size_t)p.nsplit * p.total * sizeof(float);
+    if (p.direct) return p;
+    const size_t pre = wgrad_pre_bytes(p.total, p.nsplit);
+    p.pre = pre && ws_bytes >= p.used + pre;
+    p.finish_ns = p.pre ? wgrad_pre_groups() : p.nsplit;
+    if (p.pre) p.used += pre;
+    return p;
+}
+
+template <typename T, int GEO, int TH, int TW, int BP, int NSUB, int KSUB, bool TR>
+static int launch_wgrad(const WgradArgs& a, int pairs, int nsplit, hipStream_t st) {
+    constexpr int IS = Geo<GEO>::IS, TK = Geo<GEO>::TK, NT = TK * TK;
+    constexpr int PH = (TH - 1) * IS + TK, PW = (TW - 1) * IS + TK, NI = BP / (TH * TW);
+    constexpr int OPER = BP * wgrad_pitch<T>(NSUB * 16, TR, 1) + NI * PH * PW * wgrad_pitch<T>(KSUB * 16, TR, IS);
+    constexpr int FOLD = NT * NSUB * 16 * (KSUB * 16 + 1) * 4;          // direct epilogue: all taps of the tile, fp32
+    constexpr int LDS = OPER > FOLD ? OPER : FOLD;
+    static_assert(LDS <= 160 * 1024, "LDS budget");
+    auto kern = wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR>;
+    sgx_lds_opt_in<wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR>>(LDS);
+    hipLaunchKernelGGL(kern, dim3(pairs, nsplit), dim3(256), LDS, st, a);
+    SGX_LAUNCH_CHECK("wgrad_kernel");
+    return 0;
+}
+// The one map from a plan to the instantiation that runs it: WGRAD_TABLE[geometry][fp32, bf16 plain, bf16 transpose-read][(nsub, ksub)]
+// [tile].  What exists: 3 tiles x 4 channel pairs of the 3x3 geometry (128 pixels), 3 x 2 of the stride-2 one (64 pixels, ksub 1: its
+// ksub 2 slots are null, wgrad_ch never plans them), each three times.
+typedef int (*WgradLaunch)(const WgradArgs&, int, int, hipStream_t);
+#define WG_TILES(T, GEO, BP, NS, KS, TR) \
+    {launch_wgrad<T, GEO, BP / 16, 16, BP, NS, KS, TR>, launch_wgrad<T, GEO, 8, 8, BP, NS, KS, TR>, launch_wgrad<T, GEO, 4, 4, BP, NS, KS, TR>}
+#define WG_S(T, TR) \
+    {WG_TILES(T, G3X3, 128, 1, 1, TR), WG_TILES(T, G3X3, 128, 1, 2, TR), WG_TILES(T, G3X3, 128, 2, 1, TR), WG_TILES(T, G3X3, 128, 2, 2, TR)}
+#define WG_D(T, TR) {WG_TILES(T, GDOWN, 64, 1, 1, TR), {}, WG_TILES(T, GDOWN, 64, 2, 1, TR), {}}
+static const WgradLaunch WGRAD_TABLE[2][3][4][3] = {{WG_S(float, false), WG_S(bf16_t, false), WG_S(bf16_t, true)},
+                                                    {WG_D(float, false), WG_D(bf16_t, false), WG_D(bf16_t, true)}};
+
+static int wgrad_finish(const WgradPlan& p, const WgradArgs& a, int Ip, float* ws, hipStream_t st) {
+    const float* parts = ws;
+    if (p.pre) {
+        float* out = ws + (size_t)p.nsplit * p.total;
+        hipLaunchKernelGGL(wgrad_prereduce_kernel, dim3((unsigned)((p.total / 4 + 255) / 256), p.finish_ns), dim3(256), 0, st, parts, out,
+                           p.total / 4, p.nsplit);
+        SGX_LAUNCH_CHECK("wgrad_prereduce_kernel");
+        parts = out;
+    }
+    FinishArgs f{parts, a.dw, a.db, p.finish_ns, a.O, a.I, Ip, a.mode, a.transposed, a.flip_t, a.scale, a.accumulate};
+    SGX_NOTE(0.0, 4.0 * ((double)p.finish_ns * (a.mode == SGX_PACK_S ? 9 : 16) * a.O * Ip + 9.0 * a.O * a.I), "finish %dx%d m%d tr%d ns%d",
+             a.O, a.I, a.mode, a.transposed, p.finish_ns);
+    const int e = p.epb, ne = a.O * Ip, nb = a.db ? a.O : 0;           // bias blocks trail the weight blocks
+    const dim3 grid((unsigned)((ne + e - 1) / e + (nb + e - 1) / e));
+    if (e == 64) hipLaunchKernelGGL(wgrad_finish_kernel<64>, grid, dim3(256), 0, st, f);
+    else if (e == 16) hipLaunchKernelGGL(wgrad_finish_kernel<16>, grid, dim3(256), 0, st, f);
+    else if (e == 8) hipLaunchKernelGGL(wgrad_finish_kernel<8>, grid, dim3(256), 0, st, f);
+    else hipLaunchKernelGGL(wgrad_finish_kernel<4>, grid, dim3(256), 0, st, f);
     SGX_LAUNCH_CHECK("wgrad_finish_kernel");
     return 0;
 }
 
-extern "C" size_t sgx_wgrad_ws_bytes(int taps, int B, int H, int W, int Ck, int Cn) {
-    size_t total = ((size_t)taps * Ck * Cn + Cn) * sizeof(float);
-    int pairs = (Ck / 32 > 0 ? Ck / 32 : 1) * (Cn / 32 > 0 ? Cn / 32 : 1);
-    size_t ntiles = (size_t)B * ((H + 3) / 4) * ((W + 3) / 4);
-    size_t ns = (size_t)wgrad_nsplit(pairs, ntiles > (1u << 30) ? (1 << 30) : (int)ntiles, (size_t)taps * Ck * Cn);
-    size_t need = total * ns + wgrad_pre_bytes(total / sizeof(float), (int)ns);
-    int a0, a1, a2, a3;                                             // the second-generation kernel's splits (bf16 only; harmless for fp32)
-    const int ns2 = taps == 9 ? sgx_wgrad2_plan(0, B, H, W, Ck, Cn, &a0, &a1, &a2, &a3) : sgx_wgrad2_plan(1, B, H / 2, W / 2, Ck, Cn, &a0, &a1, &a2, &a3);
-    const size_t need2 = ns2 ? total * ns2 + wgrad_pre_bytes(total / sizeof(float), ns2) : 0;
-    return need > need2 ? need : need2;
+// The body of both entry points: plan -> (generation 2 | generation 1) -> (direct | pre-reduction -> finish)
+static int wgrad_param(const char* name, int geo, WgradArgs& a, int Ip, void* ws, size_t ws_bytes, int dtype, hipStream_t st) {
+    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "%s: bad dtype", name);
+    const WgradPlan p = wgrad_plan(geo, dtype, a.B, a.Hn, a.Wn, a.Ck, a.Cn, ws_bytes);
+    if (p.rc) return p.rc;
+    a.out = static_cast<float*>(ws);
+    int rc;
+    if (p.gen == 2) rc = sgx_wgrad2_launch(geo, p.g2, a.kside, a.nside, a.out, a.B, a.Hn, a.Wn, a.Ck, a.Cn, a.want_bias, st);
+    else {
+        a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.ntiles = p.ntiles; a.direct = p.direct;
+        const WgradLaunch fn = WGRAD_TABLE[geo][dtype == SGX_F32 ? 0 : 1 + p.tr][(p.nsub - 1) * 2 + p.ksub - 1][p.tw == 16 ? 0 : (p.tw == 8 ? 1 : 2)];
+        SGX_REQUIRE(fn, SGX_EUNSUPPORTED, "%s: no wgrad_kernel for sub-tiles (%d, %d)", name, p.nsub, p.ksub);
+        rc = fn(a, p.pairs, p.nsplit, st);
+    }
+    return rc || p.direct ? rc : wgrad_finish(p, a, Ip, a.out, st);
 }
 
-extern "C" int sgx_wgrad3x3_param(const void* x, const void* dy, float* dW, float* db, void* ws, size_t ws_bytes, int B, int H,
-                                  int W, int Cx, int Cdy, int adjoint, float scale, int O, int I, int accumulate, int dtype,
-                                  void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+// An upper bound of what any launch of the shape uses, not the launcher's own plan: the first generation is sized for channel pairs of
+// 32 x 32 and one-image 4x4 tiles of the k side's grid whichever kernel runs.  The query's pairs are never more than the launcher's and its
+// tiles never fewer, so it wants no fewer splits, and the one-split rule fires here only where it fires in the launcher: the launcher's
+// workspace clamp never binds on the queried size (tests/test_wgrad_plan.py), so the size cannot change the split count and the
+// summation order.
+extern "C" size_t sgx_wgrad_ws_bytes(int taps, int B, int H, int W, int Ck, int Cn) {
+    const size_t total = (size_t)taps * Ck * Cn + Cn;
+    const int pairs = (Ck / 32 > 0 ? Ck / 32 : 1) * (Cn / 32 > 0 ? Cn / 32 : 1);
+    const size_t ntiles = (size_t)B * ((H + 3) / 4) * ((W + 3) / 4);
+    const int ns = wgrad_nsplit(pairs, ntiles > (1u << 30) ? (1 << 30) : (int)ntiles, (size_t)taps * Ck * Cn);
+    // the second generation's splits (bf16 only; harmless for fp32)
+    const int ns2 = (taps == 9 ? sgx_wgrad2_plan(0, B, H, W, Ck, Cn) : sgx_wgrad2_plan(1, B, H / 2, W / 2, Ck, Cn)).ns;
+    const size_t need = total * sizeof(float) * ns + wgrad_pre_bytes(total, ns);
+    const size_t need2 = ns2 ? total * sizeof(float) * ns2 + wgrad_pre_bytes(total, ns2) : 0;
+    return need > need2 ? need : need2;
+}
+extern "C" int sgx_wgrad_plan(int taps, int B, int H, int W, int Ck, int Cn, int dtype, size_t ws_bytes, int* out) {
+    SGX_REQUIRE((taps == 9 || taps == 16) && (dtype == SGX_F32 || dtype == SGX_BF16) && out, SGX_EINVAL, "wgrad_plan: bad args");
+    const int is = taps == 9 ? 1 : 2;
+    SGX_REQUIRE(H % is == 0 && W % is == 0, SGX_EINVAL, "wgrad_plan: odd fine size");     // as sgx_wgrad4x4s2_param
+    const WgradPlan p = wgrad_plan(taps == 9 ? G3X3 : GDOWN, dtype, B, H / is, W / is, Ck, Cn, ws_bytes);
+    const int v[SGX_WGRAD_PLAN_INTS] = {p.gen, p.th, p.tw, p.bp, p.nsub, p.ksub, p.tr, p.nsplit, p.finish_ns, p.pre, p.epb};
+    for (int i = 0; i < SGX_WGRAD_PLAN_INTS; ++i) out[i] = v[i];
+    return p.rc;
+}
+
+extern "C" int sgx_wgrad3x3_param(const void* x, const void* dy, float* dW, float* db, void* ws, size_t ws_bytes, int B, int H, int W, int Cx, int Cdy,
+                                  int adjoint, float scale, int O, int I, int accumulate, int dtype, void* stream) {
     const int Ip = adjoint ? Cdy : Cx;
     SGX_REQUIRE(!db || !adjoint, SGX_EINVAL, "wgrad3x3_param: bias gradient asked of the adjoint launch");
     SGX_REQUIRE((adjoint ? Cx : Cdy) == O && Ip >= I, SGX_EINVAL, "wgrad3x3_param: channel mismatch (Cx=%d Cdy=%d O=%d I=%d adj=%d)", Cx, Cdy, O, I, adjoint);
     WgradArgs a{x, dy, nullptr, B, H, W, H, W, Cx, Cdy, 0, 0, 0, db ? 1 : 0,
                 0, dW, db, O, I, SGX_PACK_S, adjoint, adjoint, accumulate, scale};
     SGX_NOTE(2.0 * 9 * Cx * Cdy * B * H * W, (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * (Cx + Cdy), "wgradS B%d %dx%d %dx%d", B, H, W, Cx, Cdy);
-    int ns = 0, rc;
-    if (dtype == SGX_BF16) {                                       // second-generation kernel (wgrad2.hip) where it applies
-        rc = sgx_wgrad2_launch(0, x, dy, static_cast<float*>(ws), ws_bytes, B, H, W, Cx, Cdy, db ? 1 : 0, st, &ns);
-        if (rc) return rc;
-        if (ns) return wgrad_finish(ws, dW, db, ns, O, I, Ip, SGX_PACK_S, adjoint, adjoint, scale, accumulate, st, ws_bytes);
-    }
-    if (dtype == SGX_F32) rc = wgrad_ch<float, G3X3, 128>(a, ws, ws_bytes, &ns, st);
-    else if (dtype == SGX_BF16) rc = wgrad_use_tr() ? wgrad_ch<bf16_t, G3X3, 128, true>(a, ws, ws_bytes, &ns, st) : wgrad_ch<bf16_t, G3X3, 128>(a, ws, ws_bytes, &ns, st);
-    else { SGX_REQUIRE(false, SGX_EINVAL, "wgrad3x3_param: bad dtype"); }
-    if (rc) return rc;
-    if (a.direct) return 0;
-    return wgrad_finish(ws, dW, db, ns, O, I, Ip, SGX_PACK_S, adjoint, adjoint, scale, accumulate, st, ws_bytes);
+    return wgrad_param("wgrad3x3_param", G3X3, a, Ip, ws, ws_bytes, dtype, (hipStream_t)stream);
 }
 
-extern "C" int sgx_wgrad4x4s2_param(const void* fine, const void* coarse, float* dW, float* db, void* ws, size_t ws_bytes, int B,
-                                    int H, int W, int Cfine, int Ccoarse, int mode, float scale, int O, int I, int accumulate,
-                                    int dtype, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+extern "C" int sgx_wgrad4x4s2_param(const void* fine, const void* coarse, float* dW, float* db, void* ws, size_t ws_bytes, int B, int H, int W, int Cfine,
+                                    int Ccoarse, int mode, float scale, int O, int I, int accumulate, int dtype, void* stream) {
     SGX_REQUIRE(H % 2 == 0 && W % 2 == 0, SGX_EINVAL, "wgrad4x4s2_param: odd fine size");
     SGX_REQUIRE(mode == SGX_PACK_D || mode == SGX_PACK_U || mode == SGX_PACK_UF, SGX_EINVAL, "wgrad4x4s2_param: bad mode %d", mode);
     const int transposed = mode != SGX_PACK_D;                 // kernel output is [t][coarse ch][fine ch]
@@ -1392,18 +1437,7 @@ extern "C" int sgx_wgrad4x4s2_param(const void* fine, const void* coarse, float*
     WgradArgs a{fine, coarse, nullptr, B, H, W, H / 2, W / 2, Cfine, Ccoarse, 0, 0, 0, db ? 1 : 0,
                 0, dW, db, O, I, mode, transposed, 0, accumulate, scale};
     SGX_NOTE(2.0 * 16 * Cfine * Ccoarse * B * (H / 2) * (W / 2), (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * (Cfine + Ccoarse / 4.0), "wgradD B%d fine%dx%d %dx%d", B, H, W, Cfine, Ccoarse);
-    int ns = 0, rc;
-    if (dtype == SGX_BF16) {
-        rc = sgx_wgrad2_launch(1, fine, coarse, static_cast<float*>(ws), ws_bytes, B, H / 2, W / 2, Cfine, Ccoarse, db ? 1 : 0, st, &ns);
-        if (rc) return rc;
-        if (ns) return wgrad_finish(ws, dW, db, ns, O, I, I, mode, transposed, 0, scale, accumulate, st, ws_bytes);
-    }
-    if (dtype == SGX_F32) rc = wgrad_ch<float, GDOWN, 64>(a, ws, ws_bytes, &ns, st);
-    else if (dtype == SGX_BF16) rc = wgrad_use_tr() ? wgrad_ch<bf16_t, GDOWN, 64, true>(a, ws, ws_bytes, &ns, st) : wgrad_ch<bf16_t, GDOWN, 64>(a, ws, ws_bytes, &ns, st);
-    else { SGX_REQUIRE(false, SGX_EINVAL, "wgrad4x4s2_param: bad dtype"); }
-    if (rc) return rc;
-    if (a.direct) return 0;
-    return wgrad_finish(ws, dW, db, ns, O, I, I, mode, transposed, 0, scale, accumulate, st, ws_bytes);
+    return wgrad_param("wgrad4x4s2_param", GDOWN, a, I, ws, ws_bytes, dtype, (hipStream_t)stream);
 }
 
 // =====================================================================================================

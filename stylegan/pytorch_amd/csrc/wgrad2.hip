@@ -497,61 +497,45 @@ __global__ __launch_bounds__(512, 2) void wgrad16_s_kernel(Wg2Args a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- host side
-static int wg2_ncu() { return sgx_ncu(); }
-static int wg2_switch() {                        // SGX_WGRAD2: bit 0 = the 3x3 geometry, bit 1 = the 4x4 stride-2 geometry, bit 2 = 3x3 16x16 channels (A/B)
-    static const int on = [] { const char* e = getenv("SGX_WGRAD2"); return e ? atoi(e) : 7; }();
-    return on;
-}
-static int wg2_max_ct() { static const int v = [] { const char* e = getenv("SGX_WGRAD2_MAXCT"); return e && atoi(e) > 0 ? atoi(e) : 32; }(); return v; }
+SGX_SWITCH(wg2_switch, "SGX_WGRAD2", 7)          // bit 0 = the 3x3 geometry, bit 1 = the 4x4 stride-2 geometry, bit 2 = 3x3 16x16 channels (A/B)
+SGX_SWITCH(wg2_max_ct_env, "SGX_WGRAD2_MAXCT", 0)
+static int wg2_max_ct() { return wg2_max_ct_env() > 0 ? wg2_max_ct_env() : 32; }
 
-// Which layers take these kernels, and with how many pixel splits.  geo 0: 3x3 (H, W = the common size); 1: 4x4 stride 2
-// (H, W = the COARSE size).  Returns 0 if the shape stays with the first generation.
-int sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn, int* nct_n, int* nct_k, int* kbw, int* ntiles) {
-    if (!((wg2_switch() >> geo) & 1)) return 0;
-    int th, tw, kt;
-    if (geo == 0 && Ck == 16 && Cn == 16) {           // the 16 x 16-channel weights: wgrad16_s_kernel (bit 2 of SGX_WGRAD2)
-        if (!(wg2_switch() & 4) || W % 32) return 0;
-        *nct_n = 1; *nct_k = 1; *kbw = 16;
-        *ntiles = B * ((H + 15) / 16) * (W / 32);
-        int ns = 2 * wg2_ncu() / 8 * 8;                // two blocks per CU
-        if (*ntiles < 2 * ns) ns = *ntiles / 2 / 8 * 8;
-        return ns >= 8 ? ns : 0;
-    }
-    if (geo == 0) {
-        if (Ck % 64 || Cn % 64 || W % 32 || H % 8) return 0;
-        th = 8; tw = 32; kt = 64; *kbw = 2;
-    } else {
-        if (Cn % 64 || Ck % 32 || W % 16 || H % 4) return 0;
-        th = 4; tw = 16; *kbw = Ck % 64 == 0 ? 2 : 1; kt = 32 * *kbw;
-    }
-    *nct_n = Cn / 64; *nct_k = Ck / kt;
-    *ntiles = B * (H / th) * (W / tw);
-    const int nct = *nct_n * *nct_k;
-    if (nct > 2 * wg2_max_ct()) return 0;
-    int ns = wg2_ncu() / nct / 8 * 8;              // ~ one block per CU, a multiple of 8 (one split per XCD slot)
+// Which layers take these kernels, on which tiles and with how many pixel splits.  geo 0: 3x3 (H, W = the common size); 1: 4x4 stride 2
+// (H, W = the COARSE size).  ns = 0: the shape stays with the first generation.
+Wg2Plan sgx_wgrad2_plan(int geo, int B, int H, int W, int Ck, int Cn) {
+    Wg2Plan p{};
+    if (!((wg2_switch() >> geo) & 1)) return p;
+    const bool c16 = geo == 0 && Ck == 16 && Cn == 16;   // the 16 x 16-channel weights: wgrad16_s_kernel (bit 2 of SGX_WGRAD2), ragged last tile row
+    if (c16 && (!(wg2_switch() & 4) || W % 32)) return p;
+    if (!c16 && geo == 0 && (Ck % 64 || Cn % 64 || W % 32 || H % 8)) return p;
+    if (geo == 1 && (Cn % 64 || Ck % 32 || W % 16 || H % 4)) return p;
+    p.th = c16 ? 16 : geo == 0 ? 8 : 4; p.tw = geo == 0 ? 32 : 16;      // the tiles: 16x32, 8x32, 4x16
+    p.kbw = c16 ? 16 : geo == 0 || Ck % 64 == 0 ? 2 : 1;
+    p.nct_n = c16 ? 1 : Cn / 64; p.nct_k = c16 ? 1 : Ck / (geo == 0 ? 64 : 32 * p.kbw);
+    p.tiles_x = W / p.tw; p.tiles_y = (H + p.th - 1) / p.th;
+    p.ntiles = B * p.tiles_y * p.tiles_x;
+    const int nct = p.nct_n * p.nct_k;
+    if (nct > 2 * wg2_max_ct()) return p;
+    int ns = c16 ? 2 * sgx_ncu() / 8 * 8 : sgx_ncu() / nct / 8 * 8;   // two blocks / ~ one block per CU, a multiple of 8 (one split per XCD slot)
     if (ns < 8) ns = 8;
     // big weights at low resolution (512 x 512 channels: 64 tiles, 9-17 MB of partials per split): only when every block
     // walks >= 8 pixel tiles, i.e. the operand traffic outweighs the partials (probe at 32^2: batch 32 255 -> 160 us and
     // 166 -> 107 us, batch 4 no gain / 31 -> 57 us: there the first generation's single-split no-partials path stays)
-    if (nct > wg2_max_ct() && *ntiles < 8 * ns) return 0;
-    if (*ntiles < 2 * ns) ns = *ntiles / 2 / 8 * 8;  // small problems: fewer splits, every block still pipelines >= 2 tiles
-    return ns >= 8 ? ns : 0;                        // too few pixel tiles: first generation
+    if (nct > wg2_max_ct() && p.ntiles < 8 * ns) return p;
+    if (p.ntiles < 2 * ns) ns = p.ntiles / 2 / 8 * 8;  // small problems: fewer splits, every block still pipelines >= 2 tiles
+    p.ns = ns >= 8 ? ns : 0;                        // too few pixel tiles: first generation
+    return p;
 }
 
-int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, size_t ws_bytes, int B, int H, int W, int Ck, int Cn,
-                      int want_bias, hipStream_t st, int* nsplit_out) {
-    int nct_n, nct_k, kbw, ntiles;
-    int ns = sgx_wgrad2_plan(geo, B, H, W, Ck, Cn, &nct_n, &nct_k, &kbw, &ntiles);
-    *nsplit_out = 0;
-    if (!ns) return 0;
-    const int NT = geo == 0 ? 9 : 16;
-    const size_t total = (size_t)NT * Cn * Ck + Cn;
-    if ((size_t)ns * total * sizeof(float) > ws_bytes) return 0;
+// Writes the same per-split partials as wgrad_kernel; the caller has checked that p.ns splits fit the workspace
+int sgx_wgrad2_launch(int geo, const Wg2Plan& p, const void* kside, const void* nside, float* ws, int B, int H, int W, int Ck, int Cn,
+                      int want_bias, hipStream_t st) {
+    const size_t total = (size_t)(geo == 0 ? 9 : 16) * Cn * Ck + Cn;
     Wg2Args a{static_cast<const bf16_t*>(kside), static_cast<const bf16_t*>(nside), ws, B, geo == 0 ? H : 2 * H, geo == 0 ? W : 2 * W, H, W, Ck, Cn,
-              W / (geo == 0 ? 32 : 16), H / (geo == 0 ? 8 : 4), ntiles, ns, nct_n, nct_k, want_bias, (long)total};
-    const dim3 grid((unsigned)(nct_n * nct_k * ns)), block(512);
-    if (geo == 0 && kbw == 16) {
-        a.tiles_y = (H + 15) / 16;
+              p.tiles_x, p.tiles_y, p.ntiles, p.ns, p.nct_n, p.nct_k, want_bias, (long)total};
+    const dim3 grid((unsigned)(p.nct_n * p.nct_k * p.ns)), block(512);
+    if (geo == 0 && p.kbw == 16) {
         constexpr int LDS = 2 * (16 * 32 * 32 + ((18 * 34 * 32 + 1023) / 1024) * 1024);
         static_assert(LDS >= 4 * 64 * 40 * 4, "the final reduction's scratch fits the stages");
         sgx_lds_opt_in<wgrad16_s_kernel>(LDS);
@@ -560,7 +544,7 @@ int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, 
         constexpr int LDS = 2 * (2 * 8 * 32 * 64 + 2 * ((10 * 34 * 64 + 1023) / 1024) * 1024);
         sgx_lds_opt_in<wgrad2_s_kernel<8>>(LDS);
         hipLaunchKernelGGL(wgrad2_s_kernel<8>, grid, block, LDS, st, a);
-    } else if (kbw == 2) {
+    } else if (p.kbw == 2) {
         constexpr int LDS = 2 * (2 * 4096 + 8 * 6144);
         sgx_lds_opt_in<wgrad2_d_kernel<2>>(LDS);
         hipLaunchKernelGGL(wgrad2_d_kernel<2>, grid, block, LDS, st, a);
@@ -570,6 +554,5 @@ int sgx_wgrad2_launch(int geo, const void* kside, const void* nside, float* ws, 
         hipLaunchKernelGGL(wgrad2_d_kernel<1>, grid, block, LDS, st, a);
     }
     SGX_LAUNCH_CHECK("wgrad2_kernel");
-    *nsplit_out = ns;
     return 0;
 }

@@ -39,6 +39,7 @@ SIGNATURES = {
     "sgx_conv4x4s2_down": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "sgx_conv4x4s2_up": (I, [P, P, P, I, I, I, I, I, I, P]),
     "sgx_wgrad_ws_bytes": (Z, [I, I, I, I, I, I]),
+    "sgx_wgrad_plan": (I, [I, I, I, I, I, I, I, Z, P]),
     "sgx_images_u8_to_nhwc": (I, [P, P, P, I, I, I, I, I, P]),
     "sgx_selftest_tr16": (I, [P, P]),
     "sgx_conv_splitk_ws_bytes": (Z, [I, I, I, I, I, I, I]),

@@ -1,6 +1,7 @@
 """CPU side of tests/test_gpu_wgrad_paths.py: (1) every hipLaunchKernelGGL site of csrc/wgrad2.hip and of the weight-gradient section of
 csrc/conv.hip is claimed by a row of wgrad_ref.CASES or excused by name with a reason, and the wgrad_kernel instantiations the restated
-wgrad_ch / wgrad_tile can return are exactly the ones the rows name; (2) the restated launcher rules select, for every row's own arguments,
+wgrad_ch / wgrad_tile (wgrad_ref's, not the library's: tests/test_wgrad_plan.py holds the library's plan and its compiled kernels against
+them) can return are exactly the ones the rows name; (2) the restated launcher rules select, for every row's own arguments,
 the kernels and split counts the row says, at 256 and at 304 CUs; (3) the fp64 references agree with autograd of the oracle's convolution;
 (4) both criteria pass an fp32 emulation of the kernels (per-split partials, then the finishing pass) and fail nine planted errors."""
 import collections
@@ -20,7 +21,7 @@ F, H = torch.float32, torch.bfloat16
 # Rows per environment group.  A row is a launch path someone decided to cover: dropping one has to be a decision made here too.
 ROWS = {"default": 191, "w2_0": 3, "w2_3": 3, "w2_5": 3, "w2_6": 3, "tr0": 19, "pre0": 2, "pre4": 4, "maxsplit3": 3, "blocks": 2, "maxct1": 3}
 # Sites that name no instantiation, by the text of the site
-FUNCTION_POINTER = {"kern": "wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR> through launch_wgrad's function pointer: the instantiation scan below enumerates them"}
+FUNCTION_POINTER = {"kern": "wgrad_kernel<T, GEO, TH, TW, BP, NSUB, KSUB, TR> through launch_wgrad's function pointer, one launch_wgrad per entry of WGRAD_TABLE: the instantiation scan below enumerates them"}
 
 
 def sites():
@@ -47,7 +48,7 @@ def test_every_launch_site_is_claimed_or_excused():
     with open(os.path.join(CSRC, "conv.hip")) as f:
         src = f.read()
     with open(os.path.join(CSRC, "wgrad2.hip")) as f:
-        read = set(re.findall(r'getenv\("(SGX_WGRAD[A-Z0-9_]*)"\)', src[src.index("// Weight gradients."):src.index("// Weight packing")] + f.read()))
+        read = set(re.findall(r'SGX_SWITCH\(\s*\w+\s*,\s*"(SGX_WGRAD[A-Z0-9_]*)"', src[src.index("// Weight gradients."):src.index("// Weight packing")] + f.read()))
     assert read == set(WR.ENV0) and read - {k for g in WR.GROUPS.values() for k in g} == set(WR.EXCLUDED_PATHS)
 
 
@@ -63,7 +64,7 @@ def test_a_new_kernel_or_a_dropped_row_is_noticed():
 
 
 def reachable():
-    """Every wgrad_kernel instantiation wgrad_ch and wgrad_tile can return, by enumeration over the geometry, the dtype, SGX_WGRAD_TR, the
+    """Every wgrad_kernel instantiation wgrad_ref's wgrad_ch and wgrad_tile can return, by enumeration over the geometry, the dtype, SGX_WGRAD_TR, the
     parity classes of the channel counts (multiples of 16 that are / are not multiples of 32, and the 512-channel sizes of lowres_big) and
     the size classes of the n-side grid."""
     out = set()

@@ -3,7 +3,11 @@ the rows that need process-wide switches (``python wgrad_runner.py GROUP`` with 
 stops at the first HIP error).  Each row: the library's profiler brackets the call, the kernels that ran must be exactly the row's and the
 finishing launch must report the restated split count, dW / db / the workspace sit in streaming_ref.Guarded buffers (the workspace exactly as
 large as the row says, sentinel-filled: a partial that is read without having been written is a NaN), and the values meet wgrad_ref's
-criteria: bit equality on integer rows, the chain bound on the others."""
+criteria: bit equality on integer rows, the chain bound on the others.  Before the call the row's shape and workspace are put to sgx_wgrad_plan:
+the generation, the finishing launch's ``ns`` and the pre-reduction it announces must be what the profiler then shows, and so must the split
+count where the finish note carries it (no pre-reduction); behind a pre-reduction the note shows the groups, and the split count is compared
+with the restated one the row pins."""
+import ctypes
 import json
 import os
 import re
@@ -83,8 +87,13 @@ def run(L, N, c):
         call = lambda: L.sgx_wgrad3x3_param(p(xk), p(xn), p(dW.t), p(db.t if db else None), p(ws.t), wsb, B, Hh, W, Ck, Cn, a["adjoint"], scale, O, I, acc, dtc, N.stream())
     else:
         call = lambda: L.sgx_wgrad4x4s2_param(p(xk), p(xn), p(dW.t), p(db.t if db else None), p(ws.t), wsb, B, Hh, W, Ck, Cn, WR.MODES[mode], scale, O, I, acc, dtc, N.stream())
+    said = (ctypes.c_int * 11)()
+    said_rc = L.sgx_wgrad_plan(taps, B, Hh, W, Ck, Cn, dtc, wsb, ctypes.addressof(said))
+    if said_rc:
+        L.sgx_clear_error()
     rc, recs = profiled(c.id, call)
     ran = tuple(k for k, _ in recs)
+    assert said_rc == rc, f"{c.id}: sgx_wgrad_plan returned {said_rc}, the call {rc}"
     assert rc == pl.rc == a["rc"], f"{c.id}: returned {rc} ({L.sgx_last_error().decode(errors='replace')}), expected {a['rc']}"
     assert ran == pl.kernels, f"{c.id}: launched {ran}, expected {pl.kernels} ({c.why})"
     for g, what in ((dW, "dW"), (db, "db"), (ws, "workspace")):
@@ -99,6 +108,8 @@ def run(L, N, c):
     fins = [d for k, d in recs if k.startswith("wgrad_finish_kernel")]
     got_ns = int(re.search(r"ns(\d+)$", fins[0]).group(1)) if fins else None
     assert got_ns == pl.finish_ns, f"{c.id}: the finishing launch reports ns {got_ns} ({fins}), restated {pl.finish_ns}"
+    seen = (1 if ran[0].startswith("wgrad_kernel<") else 2, pl.nsplit if WR.PRE in ran else (got_ns or 1), got_ns or 0, int(WR.PRE in ran))
+    assert (said[0], said[7], said[8], said[9]) == seen, f"{c.id}: sgx_wgrad_plan says (generation, nsplit, finishing ns, pre-reduction) = {(said[0], said[7], said[8], said[9])}, the launches show {seen}"
     ref, S, rb, Sb = WR.wgrad(xk.double(), xn.double(), mode, SR.f32(scale), I, a["adjoint"], acc, dW0.double(), db0.double(), db is not None)
     if a["data"] == "int":
         assert WR.exact_ok(c) and torch.equal(ref.float().double(), ref), c.id
