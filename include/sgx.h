@@ -95,7 +95,9 @@ int sgx_conv_splitk(int geo, const void* x, const void* w, const float* bias, vo
 
 /* Host-only query: the launch configuration a convolution of this shape resolves to (geo 0: 3x3, 1: 4x4s2 down,
  * 2: 4x4s2 up; H,W = input size).  cfg5 = {KC, TH, TW, pixels per block, output-channel sub-tiles}: the template
- * arguments of conv_kernel<T, KC, geo, TH, TW, BP, CT> as rocprofv3 prints them.                                    */
+ * arguments of conv_kernel<T, KC, geo, TH, TW, BP, CT> as rocprofv3 prints them.  geo 2 answers for the per-class
+ * transposed kernel; geo 3: the 4x4s2 up convolution as its launch runs it -- the bf16 launch without deep K-chunks
+ * runs the all-class kernel (printed as geo 3), whose configuration differs; every other launch: as geo 2.          */
 int sgx_conv_config(int geo, int B, int H, int W, int Cin, int Cout, int dtype, int* cfg5);
 /* sgx_pack_weight: runtime weight scaling + operand packing (`self.weight * self.w_mul` and the 3x3 -> 4x4 kernel
  * synthesis of models/CustomLayers.py:146-150,159-162) in one launch.  w: parameter [O][I][3][3] fp32.

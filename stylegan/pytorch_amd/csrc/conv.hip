@@ -781,10 +781,15 @@ extern "C" int sgx_conv_splitk(int geo, const void* x, const void* w, const floa
 }
 
 extern "C" int sgx_conv_config(int geo, int B, int H, int W, int Cin, int Cout, int dtype, int* cfg5) {
-    SGX_REQUIRE(geo >= 0 && geo <= 2 && cfg5, SGX_EINVAL, "conv_config: bad args");
+    SGX_REQUIRE(geo >= 0 && geo <= 3 && cfg5, SGX_EINVAL, "conv_config: bad args");
+    // geo 3: the transposed convolution as dispatch_conv resolves its launch -- the bf16 launch without deep K-chunks runs the all-class kernel
+    // (GUPA), whose candidates and block count are its own; geo 2 answers for the per-class kernel whatever the launch runs
+    const bool as_launched = geo == 3;
+    if (as_launched) geo = GUP;
     const int ohc = conv_tile_extent(geo, H), owc = conv_tile_extent(geo, W);
-    const ConvCfg c = pick_cfg(geo, B, ohc, owc, Cout);
-    cfg5[0] = dtype == SGX_F32 ? 16 : (conv_deep_k(geo, B, ohc, owc, Cin, Cout) ? 128 : (Cin % 32 == 0 ? 32 : 16));
+    const bool deep = dtype != SGX_F32 && conv_deep_k(geo, B, ohc, owc, Cin, Cout);
+    const ConvCfg c = pick_cfg((as_launched && dtype == SGX_BF16 && !deep && conv_upa_on()) ? GUPA : geo, B, ohc, owc, Cout);
+    cfg5[0] = dtype == SGX_F32 ? 16 : (deep ? 128 : (Cin % 32 == 0 ? 32 : 16));
     cfg5[1] = c.th; cfg5[2] = c.tw; cfg5[3] = c.bp; cfg5[4] = c.ct;
     return 0;
 }
