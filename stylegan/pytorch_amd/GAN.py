@@ -81,6 +81,12 @@ class DeferredLoss:
 FUSE_RGB_FADE = os.environ.get("SGX_FUSE_RGB_FADE", "1") != "0"
 
 
+def _d_real_image_grad():
+    """SGX_D_REAL_IMAGE_GRAD (A/B, default 0): 1 = the D step's final backward also fills ``real.grad``, which nothing reads.
+    Read when a step is built (every eager D step, every graph lookup), not at import."""
+    return os.environ.get("SGX_D_REAL_IMAGE_GRAD", "0") not in ("0", "")
+
+
 def _nonlinearity(name):
     """(activation module, gain) of the reference's ``nonlinearity`` argument (models/GAN.py:67-68,150-151,346-347).  The
     reference maps 'relu' to the FUNCTION ``torch.relu`` and then puts it into ``nn.Sequential`` / module attributes, which
@@ -786,10 +792,20 @@ class StyleGAN:
         self._zero_grads("d", depth)
         side = self._param_stream(two_branches=aux is not None and lazy)
         self._sched_begin("d", depth, side)
-        # conv weight / bias gradients accumulate inside the finishing kernel, on a side stream next to the backward chain
+        # conv weight / bias gradients accumulate inside the finishing kernel, on a side stream next to the backward chain.
+        # The real batch is a leaf that requires grad for the R1 penalty's own autograd.grad only: this backward is asked for the
+        # parameters' gradients alone, so the adjoint chain down to the image (rgbconv_dgrad, up2+add, the residual image output of
+        # fade_rgb_bwd) is not launched for a ``real.grad`` nobody reads.  SGX_D_REAL_IMAGE_GRAD=1: the plain backward (A/B).
+        # (The engine prunes by ``inputs=``; the Functions that read the image next to parameters are told by ``no_image_grad`` --
+        # only where what D's first layers read is the image alone: the conditional D concatenates a label embedding, a parameter.)
+        image_grad = _d_real_image_grad()
+        image_alone = getattr(self.dis, "conditional", None) is False
         try:
-            with F.accumulate_param_grads(), F.param_grad_stream(side):
-                loss.backward()
+            with F.accumulate_param_grads(), F.param_grad_stream(side), F.no_image_grad(image_alone and not image_grad):
+                if image_grad:
+                    loss.backward()
+                else:
+                    loss.backward(inputs=self._d_trainable())
         except BaseException:
             self._sched_abort()
             raise
@@ -821,6 +837,17 @@ class StyleGAN:
         else:
             self.dp.all_reduce_grads((self.dis if kind == "d" else self.gen).parameters())
 
+    def _dis_params(self):
+        d_all = self.__dict__.get("_sgx_dis_params")               # the module tree is static: walk it once
+        if d_all is None:
+            d_all = self.__dict__["_sgx_dis_params"] = list(self.dis.parameters())
+        return d_all
+
+    def _d_trainable(self):
+        """What the D step's backward is asked for: every trainable parameter of D (those of inactive resolutions are not
+        in the graph and keep ``grad`` None, as under a plain ``backward()``)."""
+        return [p for p in self._dis_params() if p.requires_grad]
+
     def _d_reduce(self):
         self._reduce("d")
 
@@ -836,10 +863,7 @@ class StyleGAN:
         self._wait_update("d")                        # data parallel: D's all-reduce + Adam overlapped the G forward above
         # the reference also back-propagates into D's parameters here and discards the result at the next
         # dis_optim.zero_grad(); skipping those weight gradients changes no observable value
-        d_all = self.__dict__.get("_sgx_dis_params")               # the module tree is static: walk it once
-        if d_all is None:
-            d_all = self.__dict__["_sgx_dis_params"] = list(self.dis.parameters())
-        d_params = [p for p in d_all if p.requires_grad]
+        d_params = self._d_trainable()
         for p in d_params:
             p.requires_grad_(False)
         try:
@@ -920,6 +944,7 @@ class StyleGAN:
         self._wait_update("d"); self._wait_update("g")          # leftovers of eager calls (the graphs update in line)
         key = (kind, int(depth), tuple(noise.shape), tuple(real_batch.shape), tuple(real_batch.stride()), real_batch.dtype,
                self.aux_stream, self.param_stream,                     # a captured graph bakes its stream structure in
+               _d_real_image_grad(),                                   # ... and whether the D step walks down to real.grad
                self.dis._diffaug_bits, self.dis.training,              # ... and whether (and from where) D's input is augmented
                None if self.dis.diffaug_override is None else self.dis.diffaug_override.data_ptr(),
                (self.dis.ada_target, self.dis.ada_interval, self.dis.ada_kimg) if self._ada_on() else None,   # ... baked into the update launch

@@ -640,13 +640,25 @@ __global__ __launch_bounds__(256) void rgbconv_wgrad_kernel(const float* __restr
     }
 }
 
-// sum of the block partials, deterministic: block = 8 outputs x 32 slices of the partial list
+// sum of the block partials, deterministic: block = 8 outputs x 32 slices of the partial list.  A slice's terms are added in the
+// order k = sl, sl + 32, ...; RC_WF_PF of them are requested before the first is used (clamped address, the add selected), so a
+// thread waits for nblk / (32 RC_WF_PF) memory round trips instead of nblk / 32
+constexpr int RC_WF_PF = 8;
 __global__ __launch_bounds__(256) void rgbconv_wfinish_kernel(const float* __restrict__ part, float* __restrict__ out, int nblk, int nout) {
     __shared__ float red[256];
     const int tid = threadIdx.x, el = tid & 7, sl = tid >> 3, e = blockIdx.x * 8 + el;
     float s = 0.f;
     if (e < nout)
-        for (int k = sl; k < nblk; k += 32) s += part[(size_t)k * nout + e];
+        for (int k0 = sl; k0 < nblk; k0 += 32 * RC_WF_PF) {
+            float v[RC_WF_PF];
+#pragma unroll
+            for (int u = 0; u < RC_WF_PF; ++u) {
+                const int k = k0 + 32 * u;
+                v[u] = part[(size_t)(k < nblk ? k : nblk - 1) * nout + e];
+            }
+#pragma unroll
+            for (int u = 0; u < RC_WF_PF; ++u) s = k0 + 32 * u < nblk ? s + v[u] : s;
+        }
     red[tid] = s;
     __syncthreads();
     if (tid < 8 && e < nout) {
@@ -661,31 +673,51 @@ __global__ __launch_bounds__(256) void rgbconv_wfinish_kernel(const float* __res
 //   dWr[i][j] = s0 sr sum_{o,ky,kx} dW'[o][j][ky][kx] W0[o][i][ky][kx];   dbr[i] = s0 bscale sum_{o,ky,kx} dW'[o][3][ky][kx] W0[o][i][ky][kx]
 //   db0[o] = dW'[o][3][1][1]  (the bias channel under the centre tap counts every pixel of the image once)
 // acc bit 0: dW0, 1: db0, 2: dWr, 3: dbr accumulate into the existing gradient instead of overwriting it.  NULL outputs are skipped.
+// Grid (rgbconv_chain_blocks): blocks 0 .. C - 1 take one input channel i of dWr / dbr each, the blocks behind them 256 elements of dW0
+// each (the first of those also db0).  A dWr / dbr sum runs over 9 C terms in the order (o, tap): the block forms all 4 x 9 C products at
+// once (every load independent of every other), parks them in LDS, and four threads add them up in that order -- the result a single
+// thread walking 9 C dependent load-multiply-adds gave, without its 9 C memory round trips.
+constexpr int RC_CHAIN_TERMS = 9 * 32;                     // 9 C products per (i, j) sum at most (C == 32)
+static int rgbconv_chain_blocks(int C) { return C + (C * C * 9 + 255) / 256; }
 __global__ __launch_bounds__(256) void rgbconv_chain_kernel(const float* __restrict__ dwp, const float* __restrict__ w0, float s0, const float* __restrict__ wr,
                                                             float sr, const float* __restrict__ br, float bscale, float* __restrict__ dw0, float* __restrict__ db0,
                                                             float* __restrict__ dwr, float* __restrict__ dbr, int acc, int C) {
+    __shared__ __attribute__((aligned(16))) float prod[4][RC_CHAIN_TERMS];
     const int tid = threadIdx.x;
-    if (dw0) {
-        for (int e = tid; e < C * C * 9; e += 256) {
+    if ((int)blockIdx.x >= C) {
+        const int blk = (int)blockIdx.x - C, e = blk * 256 + tid;
+        if (dw0 && e < C * C * 9) {
             const int o = e / (C * 9), i = (e / 9) % C, tap = e % 9, ky = tap / 3, kx = tap % 3;
             const float* d = dwp + (o * 3 + ky) * 16 + kx * 4;
             float v = s0 * sr * (d[0] * wr[i * 3] + d[1] * wr[i * 3 + 1] + d[2] * wr[i * 3 + 2]);
             if (br) v += s0 * d[3] * br[i] * bscale;
             dw0[e] = (acc & 1) ? dw0[e] + v : v;
         }
-    }
-    if (db0)
-        for (int o = tid; o < C; o += 256) {
-            const float v = dwp[(o * 3 + 1) * 16 + 4 + 3];
-            db0[o] = (acc & 2) ? db0[o] + v : v;
+        if (db0 && blk == 0 && tid < C) {
+            const float v = dwp[(tid * 3 + 1) * 16 + 4 + 3];
+            db0[tid] = (acc & 2) ? db0[tid] + v : v;
         }
-    for (int e = tid; e < C * 4; e += 256) {
-        const int i = e >> 2, j = e & 3;
+        return;
+    }
+    if (!dwr && !dbr) return;
+    const int i = (int)blockIdx.x, nterm = 9 * C;
+    for (int t = tid; t < nterm; t += 256) {               // term t = o * 9 + tap: one 16-byte load of dW' gives the products of all four j
+        const int o = t / 9, tap = t - o * 9;
+        const float4 d = *reinterpret_cast<const float4*>(dwp + (o * 3 + tap / 3) * 16 + (tap % 3) * 4);
+        const float w = w0[(o * C + i) * 9 + tap];
+        prod[0][t] = d.x * w; prod[1][t] = d.y * w; prod[2][t] = d.z * w; prod[3][t] = d.w * w;
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const int j = tid;
         float* dst = j < 3 ? (dwr ? dwr + i * 3 + j : nullptr) : (dbr ? dbr + i : nullptr);
-        if (!dst) continue;
+        if (!dst) return;
         float v = 0.f;
-        for (int o = 0; o < C; ++o)
-            for (int tap = 0; tap < 9; ++tap) v += dwp[(o * 3 + tap / 3) * 16 + (tap % 3) * 4 + j] * w0[(o * C + i) * 9 + tap];
+#pragma unroll 6
+        for (int t = 0; t < nterm; t += 4) {               // (9 C is a multiple of 4: C is 16 or 32)
+            const float4 p = *reinterpret_cast<const float4*>(&prod[j][t]);
+            v += p.x; v += p.y; v += p.z; v += p.w;
+        }
         v *= j < 3 ? s0 * sr : s0 * bscale;
         const bool a = j < 3 ? (acc & 4) : (acc & 8);
         *dst = a ? *dst + v : v;
@@ -850,7 +882,7 @@ extern "C" int sgx_rgbconv_wgrad(const float* img, const void* gz, int ones, con
     SGX_LAUNCH_CHECK("rgbconv_wgrad_kernel");
     hipLaunchKernelGGL(rgbconv_wfinish_kernel, dim3((unsigned)((nout + 7) / 8)), dim3(256), 0, st, (const float*)part, dwp, nblk, nout);
     SGX_LAUNCH_CHECK("rgbconv_wfinish_kernel");
-    hipLaunchKernelGGL(rgbconv_chain_kernel, dim3(1), dim3(256), 0, st, (const float*)dwp, w0, s0, wr, sr, br, bscale, dw0, db0, dwr, dbr, acc, C);
+    hipLaunchKernelGGL(rgbconv_chain_kernel, dim3((unsigned)rgbconv_chain_blocks(C)), dim3(256), 0, st, (const float*)dwp, w0, s0, wr, sr, br, bscale, dw0, db0, dwr, dbr, acc, C);
     SGX_LAUNCH_CHECK("rgbconv_chain_kernel");
     return 0;
 }

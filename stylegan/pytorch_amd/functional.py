@@ -40,6 +40,31 @@ def data_grad_only():
         _DATA_GRAD_ONLY -= 1
 
 
+# "no image gradient" mode, the mirror image: inside the D step's final ``loss.backward(inputs=parameters)`` nobody reads the
+# gradient towards the discriminator's input image (the real batch is a leaf that requires grad only for the R1 penalty's own
+# ``autograd.grad``).  The engine prunes the nodes that feed nothing but that leaf (``PoolForkFn``, DiffAugment); the Functions
+# that take the image next to parameters -- ``RgbConvBlurFn``, ``ConvDownFadeRgbFn``, ``RgbInFn`` -- stay on the parameters'
+# path with ``needs_input_grad`` of the image still True (it is fixed at forward time), so they ask ``_want_image_grad``.
+# The caller sets the mode only where nothing but the image (and DiffAugment's draws) reaches those inputs: not for the
+# conditional discriminator, whose label embedding -- a parameter -- is concatenated to the image's channels.
+_NO_IMAGE_GRAD = 0
+
+
+@contextlib.contextmanager
+def no_image_grad(on=True):
+    global _NO_IMAGE_GRAD
+    _NO_IMAGE_GRAD += 1 if on else 0
+    try:
+        yield
+    finally:
+        _NO_IMAGE_GRAD -= 1 if on else 0
+
+
+def _want_image_grad(ctx, k):
+    """Does input ``k`` of this Function, an image the discriminator reads, need its gradient in this backward?"""
+    return ctx.needs_input_grad[k] and not (_NO_IMAGE_GRAD and not torch.is_grad_enabled())
+
+
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
@@ -835,7 +860,7 @@ class RgbConvBlurFn(Function):
         img, w0, b0, wr, br = ctx.saved_tensors
         s0, sr = ctx.cfg
         gz = _c(gz)
-        gi = _bcall(RgbConvAdjFn, gz, w0, wr, br, s0, sr) if ctx.needs_input_grad[0] else None
+        gi = _bcall(RgbConvAdjFn, gz, w0, wr, br, s0, sr) if _want_image_grad(ctx, 0) else None
         gw0 = gb0 = gwr = gbr = None
         if not _DATA_GRAD_ONLY:
             gw0, gb0, gwr, gbr = _bcall_wgrad(img, gz, True, w0, b0, wr, br, s0, sr, ctx.needs_input_grad[1:5])
@@ -1148,7 +1173,7 @@ class ConvDownFadeRgbFn(Function):
         bits, alpha_dev, pimg, wr = ctx.saved_tensors[6:10]
         alpha, beta, ws, bs = ctx.fade
         br = ctx.br_ref()
-        need_img = ctx.needs_input_grad[3]
+        need_img = _want_image_grad(ctx, 3)
         want_w = ctx.needs_input_grad[4] and not _DATA_GRAD_ONLY
         want_b = br is not None and ctx.needs_input_grad[5] and not _DATA_GRAD_ONLY
         gpimg = gwr = gbr = None
@@ -1616,7 +1641,7 @@ class RgbInFn(Function):
         img, weight = ctx.saved_tensors
         g = _c(g)
         gi = gw = gb = None
-        if ctx.needs_input_grad[0]:
+        if _want_image_grad(ctx, 0):
             gi = _bcall(RgbOutFn, g, weight, None, ctx.wscale)
         if not _DATA_GRAD_ONLY:
             if ctx.needs_input_grad[1]:
