@@ -277,6 +277,30 @@ int sgx_ada_gates(const float* gu, const float* state, int policy_bits, int* img
 int sgx_diffaug_gated(const float* x, float* y, const float* u, const int* img_bits, int B, int H, int W, int policy_bits, int adjoint,
                       int with_bias, void* ws, size_t ws_bytes, void* stream);
 int sgx_ada_update(const float* real_logits, int B, float* state, float target, float adjust_per_image, int interval, void* stream);
+/* Pixel blitting, the first augmentation group of the ADA paper, fused into the gather of the kernels above: policy_bits a subset of
+ * 1 = color, 8 = xflip, 16 = rot90, 2 = translation, 4 = cutout, applied in that order.  u: DEVICE fp32, row b at u + b * u_stride
+ * (u_stride >= 9): u0..u6 as for sgx_diffaug, and
+ *   xflip: f = min(floor(2 u7), 1);  rot90: k = min(floor(4 u8), 3), the products in fp32; an op that is absent from the policy or
+ *          gated off for the image gives f = 0 / k = 0 whatever its uniform is.
+ *   orientation G = Rot^k o Flip, in torch terms on [3][H][W]:  G(x) = rot90(flip(x, [2]) if f else x, k, [1, 2]);  with N = H = W
+ *          flip: out[i][j] = in[i][W-1-j];  k = 1: out[i][j] = in[j][N-1-i];  k = 2: out[i][j] = in[N-1-i][N-1-j];
+ *          k = 3: out[i][j] = in[N-1-j][i].  G permutes the pixels, so G^T = G^-1 = Flip o Rot^-k.
+ * adjoint = 0: y = Mask(Shift(G(L x + b))) (b only if with_bias);  adjoint = 1: y = L(G^T(Shift^T(Mask x))).  The colour stays innermost
+ * (it commutes with G in exact arithmetic), so both per-image sums are those of sgx_diffaug, summed in its order, and an image with
+ * f = 0 and k = 0 comes out bit-identical to sgx_diffaug / sgx_diffaug_gated under the same first seven draws.  As gathers:
+ *   forward: output (i, j) -> cutout test at (i, j) -> shifted position (i + tx, j + ty), tested against the image -> the source
+ *          pixel G^-1 of that position in x;
+ *   adjoint: output (i, j) -> (a, b) = G(i, j) -> source (a - tx, b - ty) in x, tested against the image and the cutout there.
+ * img_bits == NULL: the policy for every image; else image b is transformed under (policy_bits & img_bits[b]) as in sgx_diffaug_gated.
+ * rot90 needs H == W (SGX_EINVAL, nothing launched); xflip works for any H, W.  x != y; workspace as sgx_diffaug_ws_bytes, read only
+ * when color is on.  One apply launch per call, gathers only, no atomics: bit-reproducible.
+ * sgx_ada_gates_n: sgx_ada_gates for n_ops <= 5 gate uniforms per image, row b at gu + b * gu_stride (gu_stride >= n_ops): column g gates
+ *   policy bit 1 << g (1 color, 2 translation, 4 cutout, 8 xflip, 16 rot90), the same strict fp32 < against state[0] read on the device;
+ *   policy_bits < 2^n_ops.  With the row strides one [B][14] draw serves both entries without a copy: u = r, u_stride = 14;
+ *   gu = r + 9, gu_stride = 14.  Replaces the xflip, rot90 and integer-translation steps of the augment pipe's pixel blitting. */
+int sgx_diffaug_blit(const float* x, float* y, const float* u, int u_stride, const int* img_bits, int B, int H, int W, int policy_bits,
+                     int adjoint, int with_bias, void* ws, size_t ws_bytes, void* stream);
+int sgx_ada_gates_n(const float* gu, int gu_stride, int n_ops, const float* state, int policy_bits, int* img_bits, int B, void* stream);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

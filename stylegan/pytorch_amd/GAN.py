@@ -356,7 +356,7 @@ class Discriminator(nn.Module):
                  ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
-        # 'color,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
+        # 'color,xflip,rot90,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
         # ADA (Karras et al., NeurIPS 2020) on top of the policy: each op with probability p, p steered on the device towards
@@ -420,15 +420,23 @@ class Discriminator(nn.Module):
         self.temporaryDownsampler = lambda x: F.nchw_view(F.call(F.Pool2Fn, F.nhwc(x), 0.25))
 
     # test hook, after Generator._mixing_override: a [B,7] device tensor of DiffAugment draws used by every D evaluation while set
-    # (instead of fresh torch.rand draws)
+    # (instead of fresh torch.rand draws); [B,9] when the policy has a blitting op (xflip, rot90)
     diffaug_override = None
 
-    # the same for ADA's gate uniforms: a [B,3] device tensor (op k of image b is on iff ada_gate_override[b, k] < p)
+    # the same for ADA's gate uniforms: a [B,3] device tensor (op k of image b is on iff ada_gate_override[b, k] < p); [B,5] when the
+    # policy has a blitting op (column g gates policy bit 1 << g)
     ada_gate_override = None
     _ada_real = None                      # D(real) logits of the current dis_loss (detached), until ada_step consumes them
 
+    @staticmethod
+    def _override_ok(t, B, width, what):
+        if t is not None and tuple(t.shape) != (B, width):
+            raise ValueError(f"{what} must be [{B},{width}] for this policy and batch, got {tuple(t.shape)}")
+
     def _diffaug(self, img):
         u = self.diffaug_override
+        if self._diffaug_bits & F.DIFFAUG_BLIT_BITS:
+            return self._diffaug_blit(img, u)
         if not self.ada:
             if u is None:
                 u = torch.rand(img.shape[0], 7, device=img.device)       # torch's graph-safe generator: fresh draws at every replay
@@ -441,6 +449,22 @@ class Discriminator(nn.Module):
             u = r[:, :7].contiguous() if u is None else u                 # (saved for the backward passes: contiguous once)
             gu = r[:, 7:] if gu is None else gu
         return F.call(F.DiffAugFn, img, u, self._diffaug_bits, F.ada_gates(gu, self.ada_state, self._diffaug_bits))
+
+    def _diffaug_blit(self, img, u):
+        """A policy with xflip or rot90: nine draws per image, five gates; the kernels read rows of the one [B,14] draw in place."""
+        B = img.shape[0]
+        self._override_ok(u, B, 9, "diffaug_override")
+        if not self.ada:
+            if u is None:
+                u = torch.rand(B, 9, device=img.device)
+            return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+        gu = self.ada_gate_override
+        self._override_ok(gu, B, 5, "ada_gate_override")
+        if u is None or gu is None:
+            r = torch.rand(B, 14, device=img.device)
+            u = r[:, :9] if u is None else u
+            gu = r[:, 9:] if gu is None else gu
+        return F.call(F.DiffAugFn, img, u, self._diffaug_bits, F.ada_gates_n(gu, self.ada_state, self._diffaug_bits))
 
     @property
     def ada_p(self):

@@ -11,9 +11,17 @@
 // image b is on iff its gate uniform is < p, p = state[0] read on the device) instead of one policy for the batch; an image without
 // the colour bit is gathers and zeros only (its sum-pass blocks return before loading, the apply kernel does not read their partials).
 // sgx_ada_update is the controller: one block that adds this D step's sign(D(real)) to the state and, every `interval` calls, moves p.
+//
+// Pixel blitting (the first group of the ADA paper; sgx_diffaug_blit): policy bits 8 = xflip and 16 = rot90 put an orientation
+// G = Rot^k o Flip (two more draws, u7 and u8) between the colour and the shift:  y = Mask(Shift(G(L x + b))),  z = L(G^T(Shift^T(Mask g))).
+// G is a pixel permutation, so it lives in the index arithmetic of the gather and both sum passes sum what they sum without it, in the
+// same order.  A launch without the rot90 bit reads rows (reversed in registers under a flip: diffaug_blit_row_kernel); a launch with
+// it may turn rows into columns for some of its images and stages a square tile through LDS (diffaug_blit_tile_kernel).  What a policy
+// of the first three ops launches (sgx_diffaug, sgx_diffaug_gated) is untouched by it.
 #include "common.h"
 
-enum { DA_COLOR = 1, DA_TRANSLATION = 2, DA_CUTOUT = 4 };
+enum { DA_COLOR = 1, DA_TRANSLATION = 2, DA_CUTOUT = 4, DA_XFLIP = 8, DA_ROT90 = 16 };
+enum { DA_OPS3 = DA_COLOR | DA_TRANSLATION | DA_CUTOUT, DA_OPS5 = DA_OPS3 | DA_XFLIP | DA_ROT90 };
 enum { DA_PLAIN = 0, DA_FWD = 1, DA_ADJ = 2 };      // what a unit load gathers: the input itself / Shift(.) with the output mask / Shift^T(Mask .)
 constexpr int DA_BLOCK = 256;
 constexpr int DA_PART_PIXELS = 16384;               // pixels per partial sum of the sum pass (64 partials per 1024^2 image)
@@ -219,7 +227,7 @@ static int da_run(const char* name, const float* x, float* y, const float* u, co
                   int with_bias, void* ws, size_t ws_bytes, void* stream) {
     SGX_REQUIRE(x && y && u && (!GATED || img_bits) && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "%s: bad arguments (B=%d %dx%d)", name, B, H, W);
     SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "%s: image of %dx%d too large", name, H, W);
-    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= (DA_COLOR | DA_TRANSLATION | DA_CUTOUT), SGX_EINVAL, "%s: policy bits %d", name, policy_bits);
+    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= DA_OPS3, SGX_EINVAL, "%s: policy bits %d", name, policy_bits);
     SGX_REQUIRE(x != y, SGX_EINVAL, "%s: in place is not supported (the passes gather)", name);
     if (policy_bits & DA_COLOR)
         SGX_REQUIRE(ws && ws_bytes >= sgx_diffaug_ws_bytes(B, H, W), SGX_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes,
@@ -244,6 +252,317 @@ extern "C" int sgx_diffaug_gated(const float* x, float* y, const float* u, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// Pixel blitting: the orientation G = Rot^k o Flip in the gather (definitions in include/sgx.h)
+//
+// G as an index map: G(x)[p][q] = x[row][col] with (a, b) = t ? (q, p) : (p, q), row = nr ? H-1-a : a, col = nc ? W-1-b : b, where
+// t = k & 1, nr = k >> 1, nc = f ^ (k == 1 || k == 2) (the table of sgx.h, one line per k, with the flip folded in).  Its inverse,
+// which the adjoint walks, has the same form with nr and nc exchanged when t is set.  Block-uniform, like the gated policy.
+struct DaOri { int t, nr, nc; };
+
+__device__ __forceinline__ DaOri da_orient(const float* __restrict__ u, int policy, bool inverse) {
+    const int f = (policy & DA_XFLIP) ? da_draw(u[7], 2, 1) : 0;
+    const int k = (policy & DA_ROT90) ? da_draw(u[8], 4, 3) : 0;
+    DaOri o;
+    o.t = k & 1;
+    const int nr = k >> 1, nc = f ^ (((k + 1) >> 1) & 1);
+    o.nr = (inverse && o.t) ? nc : nr;
+    o.nc = (inverse && o.t) ? nr : nc;
+    return o;
+}
+
+__device__ __forceinline__ void da_orient_at(const DaOri& o, int H, int W, int p, int q, int& row, int& col) {
+    const int a = o.t ? q : p, b = o.t ? p : q;
+    row = o.nr ? H - 1 - a : a;
+    col = o.nc ? W - 1 - b : b;
+}
+
+// Source pixel of output pixel (i, j).  Forward: G^-1 of the shifted position (i + tx, j + ty) in x (in the image exactly when the
+// shifted position is: G permutes the image).  Adjoint: (a, b) = G(i, j), then (a - tx, b - ty) in g.
+template <bool ADJ>
+__device__ __forceinline__ void da_blit_src(const DaImg& q, const DaOri& o, int H, int W, int i, int j, int& si, int& sj) {
+    if (ADJ) {
+        da_orient_at(o, H, W, i, j, si, sj);
+        si -= q.tx; sj -= q.ty;
+    } else {
+        da_orient_at(o, H, W, i + q.tx, j + q.ty, si, sj);
+    }
+}
+
+// Whether output pixel (i, j) with source (si, sj) has a value: the source in the image, and no cutout at the output pixel (forward)
+// or at the source (adjoint).
+template <bool ADJ>
+__device__ __forceinline__ bool da_blit_ok(const DaImg& q, int H, int W, int i, int j, int si, int sj) {
+    const int mi = ADJ ? si : i, mj = ADJ ? sj : j;
+    return si >= 0 && si < H && sj >= 0 && sj < W && !(mi >= q.r0 && mi < q.r1 && mj >= q.c0 && mj < q.c1);
+}
+
+// da_load with the orientation.  The four sources of a group that stays in its row (t = 0) are a contiguous run, read forwards or
+// backwards: three dwordx4 as in da_load, the pixel order reversed in registers.  Everything else (a border, a cutout edge, a turned
+// image, P = 1) goes pixel by pixel.
+template <int P, bool ADJ>
+__device__ __forceinline__ void da_load_blit(const float* __restrict__ xb, int H, int W, int i, int j0, const DaImg& q, const DaOri& o,
+                                             float (&v)[3 * P], bool (&ok)[P]) {
+    if (P == 4 && !o.t) {
+        int si, s0, s3;
+        da_blit_src<ADJ>(q, o, H, W, i, j0, si, s0);
+        s3 = o.nc ? s0 - 3 : s0 + 3;
+        const int lo = min(s0, s3);
+        const int mi = ADJ ? si : i, mj0 = ADJ ? lo : j0;                                  // where the cutout is tested
+        const bool none_cut = !(mi >= q.r0 && mi < q.r1) || mj0 + P <= q.c0 || mj0 >= q.c1;
+        if (si >= 0 && si < H && lo >= 0 && lo + P <= W && none_cut) {
+            const float* s = xb + ((size_t)si * W + lo) * 3;
+            float t[12];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const f32x4u w = reinterpret_cast<const f32x4u*>(s)[k];
+                t[4 * k] = w.x; t[4 * k + 1] = w.y; t[4 * k + 2] = w.z; t[4 * k + 3] = w.w;
+            }
+            const bool rev = o.nc != 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ok[k] = true;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = rev ? t[3 * (3 - k) + ch] : t[3 * k + ch];
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+        int si, sj;
+        da_blit_src<ADJ>(q, o, H, W, i, j0 + k, si, sj);
+        ok[k] = da_blit_ok<ADJ>(q, H, W, i, j0 + k, si, sj);
+        if (ok[k]) {
+            const float* s = xb + ((size_t)si * W + sj) * 3;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = s[ch];
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = 0.f;
+        }
+    }
+}
+
+// The image mean from the sum pass's partials (every wave, fixed order, all lanes active), the colour term and the store: the
+// arithmetic of diffaug_apply_kernel, operation by operation, so an image without a flip or a turn comes out with the same bits.
+__device__ __forceinline__ float da_blit_mean(const float* __restrict__ part, int nparts, int b, int H, int W) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    float t = 0.f;
+    for (int k = lane; k < nparts; k += WAVE) t += part[(size_t)b * nparts + k];
+    return wave_sum(t) / (3.f * (float)H * (float)W);
+}
+
+template <int P, bool ADJ>
+__device__ __forceinline__ void da_blit_finish(float (&v)[3 * P], const bool (&ok)[P], const DaImg& q, int policy, float M, int with_bias,
+                                               float* __restrict__ d) {
+    if (policy & DA_COLOR) {
+        const float cs = q.c * q.s, k0 = (1.f - q.c) * M + (with_bias && !ADJ ? q.b : 0.f);
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const float m = (v[3 * k] + v[3 * k + 1] + v[3 * k + 2]) * (1.f / 3.f);
+            const float cm = q.c * m + k0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float o = cs * (v[3 * k + ch] - m) + cm;
+                v[3 * k + ch] = (ADJ || ok[k]) ? o : 0.f;
+            }
+        }
+    }
+    if (P == 4) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) reinterpret_cast<float4*>(d)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * P; ++k) d[k] = v[k];
+    }
+}
+
+// The sum pass of a blit launch: diffaug_sum_kernel's body, statement for statement (a sum does not see a permutation, so it sums the
+// same values in the same order), with the draws a row stride apart and the gates optional (img_bits == NULL: the policy for every
+// image).  Its own copy: sharing the body through a device function changes the code the compiler emits for diffaug_sum_kernel.
+template <int P, int MODE>
+__global__ __launch_bounds__(DA_BLOCK) void diffaug_blit_sum_kernel(const float* __restrict__ x, const float* __restrict__ u, int u_stride,
+                                                                    float* __restrict__ part, int nparts, int H, int W, int policy,
+                                                                    const int* __restrict__ img_bits) {
+    const int b = blockIdx.y;
+    if (img_bits) policy &= img_bits[b];
+    if (!(policy & DA_COLOR)) return;                            // (block-uniform) nobody reads this image's partials
+    const DaImg q = da_params(u + (size_t)u_stride * b, H, W, policy);
+    const float* xb = x + (size_t)b * H * W * 3;
+    const int upr = W / P, nunits = H * upr;
+    constexpr int UPT = DA_PART_PIXELS / (DA_BLOCK * P);                               // units per thread
+    float acc = 0.f;
+#pragma unroll 4
+    for (int it = 0; it < UPT; ++it) {
+        const int unit = (blockIdx.x * UPT + it) * DA_BLOCK + threadIdx.x;
+        if (unit < nunits) {
+            const int i = unit / upr, j0 = (unit - i * upr) * P;
+            float v[3 * P]; bool ok[P];
+            da_load<P, MODE>(xb, H, W, i, j0, q, v, ok);
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 3 * P; ++k) s += v[k];
+            acc += s;
+        }
+    }
+    __shared__ float red[DA_BLOCK / WAVE];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = red[0];
+#pragma unroll
+        for (int w = 1; w < DA_BLOCK / WAVE; ++w) t += red[w];
+        part[(size_t)b * nparts + blockIdx.x] = t;
+    }
+}
+
+// Row path: diffaug_apply_kernel with the orientation.  grid (ceil(units / DA_BLOCK), B).
+template <int P, bool ADJ>
+__global__ __launch_bounds__(DA_BLOCK) void diffaug_blit_row_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ u,
+                                                                    int u_stride, const float* __restrict__ part, int nparts, int H, int W,
+                                                                    int policy, int with_bias, const int* __restrict__ img_bits) {
+    const int b = blockIdx.y;
+    if (img_bits) policy &= img_bits[b];
+    const float* ub = u + (size_t)u_stride * b;
+    const int upr = W / P;
+    const int unit = blockIdx.x * DA_BLOCK + threadIdx.x;
+    const DaImg q = da_params(ub, H, W, policy);
+    const DaOri o = da_orient(ub, policy, ADJ);
+    float M = 0.f;
+    if (policy & DA_COLOR) M = da_blit_mean(part, nparts, b, H, W);
+    if (unit >= H * upr) return;
+    const int i = unit / upr, j0 = (unit - i * upr) * P;
+    float v[3 * P]; bool ok[P];
+    da_load_blit<P, ADJ>(x + (size_t)b * H * W * 3, H, W, i, j0, q, o, v, ok);
+    da_blit_finish<P, ADJ>(v, ok, q, policy, M, with_bias, y + (((size_t)b * H + i) * W + j0) * 3);
+}
+
+// Tile path (H == W, W % 4 == 0, 16-byte aligned bases): a block owns a DA_TILE x DA_TILE output tile.  Under every orientation the
+// sources of the tile are a DA_TILE x DA_TILE square of the input (shifted, mirrored, turned: the index map is affine with unit steps),
+// so the block reads that square row by row -- thread (r, c) the four pixels (r, 4c .. 4c+3), eight lanes a run of 384 contiguous
+// bytes, three cache lines -- into LDS, and after one barrier every thread picks the four pixels of its output group out of LDS, along
+// a row or along a column, and stores them as the row path does (three 16-byte stores).  Pixels outside the image are neither read nor
+// staged; the output side tests the source before it reads LDS, so nothing unstaged is read.
+//
+// LDS row stride: 3 * DA_TILE + 3 = 99 floats, all accesses one float wide (the stride is odd, a pixel is 12 bytes: nothing wider
+// is aligned).  A 4-byte LDS access is served in two groups of 32 lanes on 32 banks; 32 consecutive lanes are (r, c) = (r0 .. r0+3,
+// 0 .. 7).  Staging writes float m of the group to r * 99 + 12 c + m: bank 3 r + 12 c (mod 32), r < 4, c < 8.  A row-wise read of
+// pixel k, channel ch is at row * 99 + 3 (4 c + k) + ch: 3 r + 12 c again.  A column-wise read is at (4 c + k) * 99 + 3 r + ch, and
+// 4 * 99 = 12 (mod 32): 3 r + 12 c a third time (a mirrored direction negates a term).  {12 c mod 32} = {0, 4, .., 28} and
+// {3 r} = {0, 3, 6, 9} give 32 different banks: no access conflicts.  A stride that is a multiple of 4 (for 16-byte LDS accesses)
+// would make 4 * stride a multiple of 16 and put the eight c of a column-wise read on two banks.
+constexpr int DA_TILE = 32;
+constexpr int DA_TILE_STRIDE = 3 * DA_TILE + 3;
+static_assert(DA_TILE * DA_TILE == 4 * DA_BLOCK && DA_TILE == 4 * 8, "one group of four pixels per thread, eight groups per tile row");
+
+template <bool ADJ>
+__global__ __launch_bounds__(DA_BLOCK) void diffaug_blit_tile_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ u,
+                                                                     int u_stride, const float* __restrict__ part, int nparts, int N, int tiles,
+                                                                     int policy, int with_bias, const int* __restrict__ img_bits) {
+    __shared__ float tile[DA_TILE * DA_TILE_STRIDE];
+    const int b = blockIdx.y;
+    if (img_bits) policy &= img_bits[b];
+    const float* ub = u + (size_t)u_stride * b;
+    const DaImg q = da_params(ub, N, N, policy);
+    const DaOri o = da_orient(ub, policy, ADJ);
+    float M = 0.f;
+    if (policy & DA_COLOR) M = da_blit_mean(part, nparts, b, N, N);
+    const int ti = blockIdx.x / tiles, tj = blockIdx.x - ti * tiles;
+    const int I0 = ti * DA_TILE, J0 = tj * DA_TILE;
+    const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+    int ra, ca, rb, cb;                                          // the source square: from the sources of two opposite corners
+    da_blit_src<ADJ>(q, o, N, N, I0, J0, ra, ca);
+    da_blit_src<ADJ>(q, o, N, N, I0 + DA_TILE - 1, J0 + DA_TILE - 1, rb, cb);
+    const int sr0 = min(ra, rb), sc0 = min(ca, cb);
+    const float* xb = x + (size_t)b * N * N * 3;
+    {
+        const int row = sr0 + r, col = sc0 + 4 * c;
+        float* l = tile + r * DA_TILE_STRIDE + 12 * c;
+        if (row >= 0 && row < N) {
+            if (col >= 0 && col + 4 <= N) {
+                const float* s = xb + ((size_t)row * N + col) * 3;                         // 4-byte aligned: the shift moves by whole pixels
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const f32x4u w = reinterpret_cast<const f32x4u*>(s)[k];
+                    l[4 * k] = w.x; l[4 * k + 1] = w.y; l[4 * k + 2] = w.z; l[4 * k + 3] = w.w;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (col + k >= 0 && col + k < N) {
+                        const float* s = xb + ((size_t)row * N + (col + k)) * 3;
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch) l[3 * k + ch] = s[ch];
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int i = I0 + r, j0 = J0 + 4 * c;
+    if (i >= N || j0 >= N) return;                               // the tile overhangs the image (N % 4 == 0: whole groups)
+    float v[12]; bool ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int si, sj;
+        da_blit_src<ADJ>(q, o, N, N, i, j0 + k, si, sj);
+        ok[k] = da_blit_ok<ADJ>(q, N, N, i, j0 + k, si, sj);
+        const float* l = tile + (si - sr0) * DA_TILE_STRIDE + (sj - sc0) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = ok[k] ? l[ch] : 0.f;
+    }
+    da_blit_finish<4, ADJ>(v, ok, q, policy, M, with_bias, y + (((size_t)b * N + i) * N + j0) * 3);
+}
+
+extern "C" int sgx_diffaug_blit(const float* x, float* y, const float* u, int u_stride, const int* img_bits, int B, int H, int W, int policy_bits,
+                                int adjoint, int with_bias, void* ws, size_t ws_bytes, void* stream) {
+    const char* name = "diffaug_blit";
+    SGX_REQUIRE(x && y && u && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "%s: bad arguments (B=%d %dx%d)", name, B, H, W);
+    SGX_REQUIRE(u_stride >= 9, SGX_EINVAL, "%s: draws %d floats apart, need at least 9", name, u_stride);
+    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "%s: image of %dx%d too large", name, H, W);
+    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= DA_OPS5, SGX_EINVAL, "%s: policy bits %d", name, policy_bits);
+    SGX_REQUIRE(!(policy_bits & DA_ROT90) || H == W, SGX_EINVAL, "%s: rot90 needs square images, got %dx%d", name, H, W);
+    SGX_REQUIRE(x != y, SGX_EINVAL, "%s: in place is not supported (the passes gather)", name);
+    if (policy_bits & DA_COLOR)
+        SGX_REQUIRE(ws && ws_bytes >= sgx_diffaug_ws_bytes(B, H, W), SGX_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes,
+                    sgx_diffaug_ws_bytes(B, H, W));
+    hipStream_t st = (hipStream_t)stream;
+    const int nparts = da_nparts(H, W);
+    float* part = (float*)ws;
+    const char* dir = adjoint ? "adj" : "fwd";
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    if (policy_bits & DA_COLOR) {
+        SGX_NOTE(0.0, 12.0 * B * H * W, "diffaug_blit_sum B%d %dx%d %s", B, H, W, dir);
+        const dim3 grid(nparts, B);
+        if (vec && adjoint) hipLaunchKernelGGL((diffaug_blit_sum_kernel<4, DA_ADJ>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
+        else if (vec) hipLaunchKernelGGL((diffaug_blit_sum_kernel<4, DA_PLAIN>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
+        else if (adjoint) hipLaunchKernelGGL((diffaug_blit_sum_kernel<1, DA_ADJ>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
+        else hipLaunchKernelGGL((diffaug_blit_sum_kernel<1, DA_PLAIN>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
+    }
+    // one apply launch: the tile path wherever an image of the launch may be turned and groups of four are whole and aligned, the row
+    // path (four pixels per lane) without the rot90 bit, the per-pixel path for everything else
+    if (vec && (policy_bits & DA_ROT90)) {
+        const int tiles = (W + DA_TILE - 1) / DA_TILE;
+        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_tile B%d %dx%d %s", B, H, W, dir);
+        if (adjoint) hipLaunchKernelGGL((diffaug_blit_tile_kernel<true>), dim3(tiles * tiles, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, W, tiles, policy_bits, with_bias, img_bits);
+        else hipLaunchKernelGGL((diffaug_blit_tile_kernel<false>), dim3(tiles * tiles, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, W, tiles, policy_bits, with_bias, img_bits);
+    } else if (vec) {
+        const unsigned gx = (unsigned)(((size_t)H * (W / 4) + DA_BLOCK - 1) / DA_BLOCK);
+        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_row B%d %dx%d %s", B, H, W, dir);
+        if (adjoint) hipLaunchKernelGGL((diffaug_blit_row_kernel<4, true>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+        else hipLaunchKernelGGL((diffaug_blit_row_kernel<4, false>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+    } else {
+        const unsigned gx = (unsigned)(((size_t)H * W + DA_BLOCK - 1) / DA_BLOCK);
+        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_px B%d %dx%d %s", B, H, W, dir);
+        if (adjoint) hipLaunchKernelGGL((diffaug_blit_row_kernel<1, true>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+        else hipLaunchKernelGGL((diffaug_blit_row_kernel<1, false>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+    }
+    SGX_LAUNCH_CHECK(name);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // ADA: the per-image gates and the controller (definitions in include/sgx.h)
 constexpr int ADA_BLOCK = 256;
 
@@ -258,11 +577,34 @@ __global__ __launch_bounds__(ADA_BLOCK) void ada_gates_kernel(const float* __res
 
 extern "C" int sgx_ada_gates(const float* gu, const float* state, int policy_bits, int* img_bits, int B, void* stream) {
     SGX_REQUIRE(gu && state && img_bits && B > 0, SGX_EINVAL, "ada_gates: bad arguments (B=%d)", B);
-    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= (DA_COLOR | DA_TRANSLATION | DA_CUTOUT), SGX_EINVAL, "ada_gates: policy bits %d", policy_bits);
+    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= DA_OPS3, SGX_EINVAL, "ada_gates: policy bits %d", policy_bits);
     SGX_NOTE(0.0, 16.0 * B, "ada_gates B%d", B);
     hipLaunchKernelGGL(ada_gates_kernel, dim3((B + ADA_BLOCK - 1) / ADA_BLOCK), dim3(ADA_BLOCK), 0, (hipStream_t)stream, gu, state, img_bits,
                        policy_bits, B);
     SGX_LAUNCH_CHECK("ada_gates");
+    return 0;
+}
+
+// The gates of up to five ops: column g of a row of gu (rows gu_stride floats apart) gates bit 1 << g.
+__global__ __launch_bounds__(ADA_BLOCK) void ada_gates_n_kernel(const float* __restrict__ gu, int gu_stride, int n_ops, const float* __restrict__ state,
+                                                                int* __restrict__ img_bits, int policy, int B) {
+    const int b = blockIdx.x * ADA_BLOCK + threadIdx.x;
+    if (b >= B) return;
+    const float p = state[0];
+    const float* g = gu + (size_t)gu_stride * b;
+    int on = 0;
+    for (int k = 0; k < n_ops; ++k) on |= g[k] < p ? 1 << k : 0;
+    img_bits[b] = policy & on;
+}
+
+extern "C" int sgx_ada_gates_n(const float* gu, int gu_stride, int n_ops, const float* state, int policy_bits, int* img_bits, int B, void* stream) {
+    SGX_REQUIRE(gu && state && img_bits && B > 0, SGX_EINVAL, "ada_gates_n: bad arguments (B=%d)", B);
+    SGX_REQUIRE(n_ops >= 1 && n_ops <= 5 && gu_stride >= n_ops, SGX_EINVAL, "ada_gates_n: %d ops, rows %d floats apart", n_ops, gu_stride);
+    SGX_REQUIRE(policy_bits >= 0 && policy_bits < (1 << n_ops), SGX_EINVAL, "ada_gates_n: policy bits %d for %d ops", policy_bits, n_ops);
+    SGX_NOTE(0.0, (4.0 * n_ops + 4.0) * B, "ada_gates_n B%d", B);
+    hipLaunchKernelGGL(ada_gates_n_kernel, dim3((B + ADA_BLOCK - 1) / ADA_BLOCK), dim3(ADA_BLOCK), 0, (hipStream_t)stream, gu, gu_stride, n_ops, state,
+                       img_bits, policy_bits, B);
+    SGX_LAUNCH_CHECK("ada_gates_n");
     return 0;
 }
 

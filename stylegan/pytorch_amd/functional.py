@@ -2308,13 +2308,16 @@ def nchw_view(x_nhwc):
 # ---------------------------------------------------------------------------------------------------
 # DiffAugment (Zhao et al., NeurIPS 2020) of the discriminator's fp32 NHWC RGB input, ``sgx_diffaug``: A x + b with A linear per
 # image (colour, translation, cutout for the seven draws u[b]).  The chain DiffAugFn -> DiffAugAdjFn -> DiffAugLinFn -> DiffAugAdjFn
-# closes under differentiation, so the R1 penalty's double backward runs through it.
-DIFFAUG_OPS = ("color", "translation", "cutout")          # bit k of the kernels' policy argument: DIFFAUG_OPS[k]
+# closes under differentiation, so the R1 penalty's double backward runs through it.  With ``xflip`` or ``rot90`` in the policy (pixel
+# blitting, Karras et al., NeurIPS 2020) the draws are nine per image and the same chain runs on ``sgx_diffaug_blit``.
+DIFFAUG_OPS = ("color", "xflip", "rot90", "translation", "cutout")          # the canonical order: the order the ops are applied in
+DIFFAUG_BITS = {"color": 1, "translation": 2, "cutout": 4, "xflip": 8, "rot90": 16}    # the kernels' policy bits (not the op's index)
+DIFFAUG_BLIT_BITS = DIFFAUG_BITS["xflip"] | DIFFAUG_BITS["rot90"]
 
 
 def diffaug_policy_bits(policy):
-    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,translation,cutout`` in that (canonical) order,
-    each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
+    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout`` in that
+    (canonical) order, each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
     if policy is None:
         return 0
     if not isinstance(policy, str):
@@ -2326,33 +2329,43 @@ def diffaug_policy_bits(policy):
         k = DIFFAUG_OPS.index(name)
         if k <= last:
             raise ValueError(f"DiffAugment policy {policy!r}: ops must appear once each, in the order {','.join(DIFFAUG_OPS)}")
-        bits |= 1 << k
+        bits |= DIFFAUG_BITS[name]
         last = k
     return bits
 
 
 def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
-    x, u = _c(x), _c(u)
+    x = _c(x)
     if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
         raise N.SgxError(f"diffaug: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
     B, H, W, _ = x.shape
-    if tuple(u.shape) != (B, 7) or u.dtype != torch.float32 or u.device != x.device:
-        raise N.SgxError(f"diffaug: need fp32 [{B},7] draws on {x.device}, got {tuple(u.shape)} {u.dtype} on {u.device}")
+    blit = bool(bits & DIFFAUG_BLIT_BITS)
+    nu = 9 if blit else 7
+    if blit:                                                 # rows of a wider draw (ADA: [B,14]) are used in place, a row stride apart
+        if u.dim() != 2 or u.stride(1) != 1 or u.stride(0) < nu:
+            u = _c(u)
+    else:
+        u = _c(u)
+    if tuple(u.shape) != (B, nu) or u.dtype != torch.float32 or u.device != x.device:
+        raise N.SgxError(f"diffaug: need fp32 [{B},{nu}] draws on {x.device}, got {tuple(u.shape)} {u.dtype} on {u.device}")
+    if img_bits is not None and (tuple(img_bits.shape) != (B,) or img_bits.dtype != torch.int32 or img_bits.device != x.device):
+        raise N.SgxError(f"diffaug: need int32 [{B}] image bits on {x.device}, got {tuple(img_bits.shape)} {img_bits.dtype} on "      # ADA
+                         f"{img_bits.device}")
     y = torch.empty_like(x)
     L = N.lib()
     ws, nb = None, 0
     if bits & 1:
         nb = L.sgx_diffaug_ws_bytes(B, H, W)
         ws = N.workspace(nb, x.device)
-    if img_bits is None:
+    if blit:
+        N.check(L.sgx_diffaug_blit(N.ptr(x), N.ptr(y), u.data_ptr(), u.stride(0), N.ptr(None if img_bits is None else _c(img_bits)), B, H, W,
+                                   int(bits), int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream()), "sgx_diffaug_blit")
+    elif img_bits is None:
         N.check(L.sgx_diffaug(N.ptr(x), N.ptr(y), N.ptr(u), B, H, W, int(bits), int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream()),
                 "sgx_diffaug")
-        return y
-    if tuple(img_bits.shape) != (B,) or img_bits.dtype != torch.int32 or img_bits.device != x.device:        # ADA: per-image ops
-        raise N.SgxError(f"diffaug: need int32 [{B}] image bits on {x.device}, got {tuple(img_bits.shape)} {img_bits.dtype} on "
-                         f"{img_bits.device}")
-    N.check(L.sgx_diffaug_gated(N.ptr(x), N.ptr(y), N.ptr(u), N.ptr(_c(img_bits)), B, H, W, int(bits), int(adjoint), int(with_bias),
-                                N.ptr(ws), nb, N.stream()), "sgx_diffaug_gated")
+    else:                                                    # ADA: per-image ops
+        N.check(L.sgx_diffaug_gated(N.ptr(x), N.ptr(y), N.ptr(u), N.ptr(_c(img_bits)), B, H, W, int(bits), int(adjoint), int(with_bias),
+                                    N.ptr(ws), nb, N.stream()), "sgx_diffaug_gated")
     return y
 
 
@@ -2360,8 +2373,8 @@ def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
 # img_bits[b] (``sgx_diffaug_gated``) and ``bits`` is the union.  It is saved next to ``u`` and handed down the chain, so every pass of
 # one D evaluation -- adjoint, linear part, the R1 double backward -- sees the gates of its forward.
 class DiffAugFn(Function):
-    """y = Mask(Shift(L x + b)) with the draws ``u`` [B,7] (no gradient); backward = the adjoint (DiffAugAdjFn), none when x needs
-    no gradient (the D step's fakes)."""
+    """y = Mask(Shift(G(L x + b))) with the draws ``u`` [B,7] ([B,9] with a blitting op in ``bits``; G the identity without one; no
+    gradient); backward = the adjoint (DiffAugAdjFn), none when x needs no gradient (the D step's fakes)."""
 
     @staticmethod
     def forward(ctx, x, u, bits, img_bits=None):
@@ -2378,7 +2391,7 @@ class DiffAugFn(Function):
 
 
 class DiffAugAdjFn(Function):
-    """A^T g = L(Shift^T(Mask g)); backward = A without the bias (DiffAugLinFn)."""
+    """A^T g = L(G^T(Shift^T(Mask g))); backward = A without the bias (DiffAugLinFn)."""
 
     @staticmethod
     def forward(ctx, g, u, bits, img_bits=None):
@@ -2393,7 +2406,7 @@ class DiffAugAdjFn(Function):
 
 
 class DiffAugLinFn(Function):
-    """A x = Mask(Shift(L x)) (the linear part of DiffAugFn); backward = DiffAugAdjFn."""
+    """A x = Mask(Shift(G(L x))) (the linear part of DiffAugFn); backward = DiffAugAdjFn."""
 
     @staticmethod
     def forward(ctx, x, u, bits, img_bits=None):
@@ -2422,6 +2435,21 @@ def ada_gates(gu, state, bits):
     _ada_state_ok(state, gu.device, "ada_gates")
     out = torch.empty(gu.shape[0], dtype=torch.int32, device=gu.device)
     N.check(N.lib().sgx_ada_gates(N.ptr(gu), N.ptr(state), int(bits), N.ptr(out), gu.shape[0], N.stream()), "sgx_ada_gates")
+    return out
+
+
+def ada_gates_n(gu, state, bits):
+    """``ada_gates`` for a policy with blitting ops: gu fp32 [B,5] uniforms (rows of a wider draw are read in place), column g gating
+    policy bit ``1 << g`` -> int32 [B]."""
+    if gu.dim() != 2 or gu.shape[1] != 5 or gu.dtype != torch.float32:
+        raise N.SgxError(f"ada_gates_n: need fp32 [B,5] uniforms, got {tuple(gu.shape)} {gu.dtype}")
+    if gu.stride(1) != 1 or gu.stride(0) < 5:
+        gu = _c(gu)
+    _ada_state_ok(state, gu.device, "ada_gates_n")
+    N.ptr(state)                                             # (refuses CPU tensors: gu is on the state's device)
+    out = torch.empty(gu.shape[0], dtype=torch.int32, device=gu.device)
+    N.check(N.lib().sgx_ada_gates_n(gu.data_ptr(), gu.stride(0), 5, N.ptr(state), int(bits), N.ptr(out), gu.shape[0], N.stream()),
+            "sgx_ada_gates_n")
     return out
 
 

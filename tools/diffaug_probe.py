@@ -14,6 +14,12 @@
       gate and the controller launch -- prints one JSON line.
   python tools/diffaug_probe.py --ada-ab [--batches 4 --repeats 4 --steps 8]
       step time as in --ab, the policy alone vs ADA on top of it with p pinned to 1 (every image gated on: what ADA's own launches cost).
+  python tools/diffaug_probe.py --blit-kernels [--batches 4,32 --res 1024 --iters 20]
+      the pixel-blitting apply kernels against today's apply kernel on the same tensors, forward and adjoint, per launch from the
+      library's own profiler (HIP events around every kernel; min and median over ``iters`` launches, variants interleaved): the row
+      path with flips, the tile path with every k odd, with mixed k and with the identity orientation -- prints one JSON line.
+  python tools/diffaug_probe.py --blit-ab [--batches 4,32 --repeats 4 --steps 8]
+      step time as in --ab, color,translation,cutout vs color,xflip,rot90,translation,cutout.
 """
 import argparse
 import csv
@@ -30,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 POLICY = "color,translation,cutout"
+FULL_POLICY = "color,xflip,rot90,translation,cutout"
 
 
 def kernels(a):
@@ -60,13 +67,14 @@ def stats(a):
     print(json.dumps(dict(batch=a.batch, res=a.res, kernels=rows)))
 
 
-def ab(a):
+def ab(a, base="", policy=POLICY):
     import bench
     from stylegan.pytorch_amd import functional as F
     cfg = bench.CONFIGS["ffhq1024"]
     dev = torch.device("cuda:0")
     args = argparse.Namespace(dtype="bf16", graphs="on", alpha=0.5)
-    out = dict(box=socket.gethostname(), commit=a.commit, config="ffhq1024", dtype="bf16", graphs=True, policy=POLICY, blocks=[])
+    out = dict(box=socket.gethostname(), commit=a.commit, config="ffhq1024", dtype="bf16", graphs=True, policy=policy, base_policy=base,
+               blocks=[])
     for B in [int(b) for b in a.batches.split(",")]:
         sg = bench.make_stylegan(args, cfg, dev, None)
         res, depth = cfg["resolution"], cfg["depth"]
@@ -83,11 +91,11 @@ def ab(a):
             torch.cuda.synchronize()
             return (time.perf_counter() - t) / n * 1e3
 
-        for p in ("", POLICY):
+        for p in (base, policy):
             run(p, 4)                                                # 2 eager calls + capture + a replay per half-iteration and policy
         times = {"off": [], "on": []}
         for r in range(a.repeats):
-            order = [("off", ""), ("on", POLICY)] if r % 2 == 0 else [("on", POLICY), ("off", "")]
+            order = [("off", base), ("on", policy)] if r % 2 == 0 else [("on", policy), ("off", base)]
             for key, p in order:
                 times[key].append(run(p, a.steps))
         off, on = min(times["off"]), min(times["on"])
@@ -132,6 +140,48 @@ def ada_kernels(a):
         gu, lg = torch.rand(B, 3, device="cuda"), torch.randn(B, device="cuda")
         blk["ada_gates"] = _timed(lambda: F.ada_gates(gu, state, 7), a.iters)
         blk["ada_update"] = _timed(lambda: F.ada_update(lg, state, 0.6, 1e-12, 4), a.iters)
+        out["blocks"].append(blk)
+        del x
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def blit_kernels(a):
+    import statistics
+    from stylegan.pytorch_amd import functional as F
+    from stylegan.pytorch_amd import native as N
+    R = a.res
+    out = dict(box=socket.gethostname(), commit=a.commit, res=R, iters=a.iters,
+               what="us per launch of the apply kernel [min, median] (the library's profiler: HIP events around every kernel; the sum "
+                    "pass is the same launch shape in every variant and reported once per variant as sum_us)", blocks=[])
+    for B in [int(b) for b in a.batches.split(",")]:
+        x = torch.randn(B, R, R, 3, device="cuda")
+        u = torch.rand(B, 9, device="cuda")
+        odd, ident = u.clone(), u.clone()
+        odd[:, 8] = torch.where(torch.arange(B, device="cuda") % 2 == 0, 0.3, 0.8)        # k = 1, 3
+        ident[:, 7:] = 0
+        u7 = u[:, :7].contiguous()
+        variants = {"today": (u7, 7), "row_flips": (u, 7 | 8), "tile_k_odd": (odd, 31), "tile_mixed_k": (u, 31), "tile_identity": (ident, 31)}
+        blk = dict(batch=B)
+        for mode, adj, bias in (("fwd", False, True), ("adj", True, False)):
+            for name, (uu, bits) in variants.items():
+                F._diffaug(x, uu, bits, adj, bias)                                      # warm
+            torch.cuda.synchronize()
+            times = {name: dict(apply=[], sum=[]) for name in variants}
+            for _ in range(a.iters):
+                for name, (uu, bits) in variants.items():
+                    N.prof_start(1)
+                    F._diffaug(x, uu, bits, adj, bias)
+                    torch.cuda.synchronize()
+                    N.prof_start(0)
+                    for rec in N.prof_records():
+                        times[name]["sum" if "_sum" in rec[4].split(" ")[0] else "apply"].append(rec[1] * 1e3)
+            for name, t in times.items():
+                blk[f"{mode}_{name}"] = [round(min(t["apply"]), 2), round(statistics.median(t["apply"]), 2)]
+                blk[f"{mode}_{name}_sum_us"] = round(min(t["sum"]), 2)
+            for name in variants:
+                if name != "today":
+                    blk[f"{mode}_{name}_vs_today"] = round(blk[f"{mode}_{name}"][0] / blk[f"{mode}_today"][0], 3)
         out["blocks"].append(blk)
         del x
         torch.cuda.empty_cache()
@@ -191,6 +241,8 @@ def main():
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--ada-kernels", action="store_true")
     ap.add_argument("--ada-ab", action="store_true")
+    ap.add_argument("--blit-kernels", action="store_true")
+    ap.add_argument("--blit-ab", action="store_true")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=10)
@@ -209,8 +261,12 @@ def main():
         ada_kernels(a)
     elif a.ada_ab:
         ada_ab(a)
+    elif a.blit_kernels:
+        blit_kernels(a)
+    elif a.blit_ab:
+        ab(a, base=POLICY, policy=FULL_POLICY)
     else:
-        ap.error("one of --kernels, --stats, --ab, --ada-kernels, --ada-ab")
+        ap.error("one of --kernels, --stats, --ab, --ada-kernels, --ada-ab, --blit-kernels, --blit-ab")
 
 
 if __name__ == "__main__":
