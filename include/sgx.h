@@ -327,6 +327,23 @@ size_t sgx_gepi_ws_bytes(int B, int HW, int C);
 int sgx_gepi_fwd(const void* x, const float* bias, const float* noise, const float* nw, const float* style, void* y,
                  float* mean, float* rstd, void* ws, size_t ws_bytes, const double* pre_part, int pre_npart, int B, int HW,
                  int C, int flags, int dtype, void* stream);
+/* Host-only query: what sgx_gepi_fwd / sgx_gepi_bwd / sgx_gepi_stats (entry SGX_GEPI_PLAN_FWD / _BWD / _STATS) will launch for this shape;
+ * pre: producer partials given (pre_part != NULL) or not; the workspace is taken as sufficient.  The launchers execute the same plan.
+ * out[SGX_GEPI_PLAN_INTS], the kernels in launch order being [0] alone, or [1], [3], [4], [12] and, in the backward, gepi_fin_bwd2:
+ *   [0]  one launch for the whole direction: 0 no, 1 gepi_small_fwd / _bwd<T, 256, 2>, 2 <T, 512, 4> (the backward: + gepi_fin_bwd2)
+ *   [1]  the reduction pass runs: gepi_pass<T, 0> (forward, statistics) / gepi_pass<T, 1> (backward)
+ *   [2]  the finalize reads the producer's partials instead of that pass's
+ *   [3]  gepi_fin_stats (forward, statistics) / gepi_fin_bwd1 (backward): 0 none, 1 a launch of its own, 2 the same, also writing the
+ *        coefficient table of the short-lived apply kernel, 3 folded into the apply kernel
+ *   [4]  the apply kernel: 0 none (statistics), 1 gepi_apply<T> / gepi_pass<T, 2, [5]>, 2 the short-lived blocks gepi_apply1<T> / gepi_bwd2s<T>
+ *   [5]  its accesses carry the nontemporal hint
+ *   [6..10]  the geometry of gepi_pass / gepi_apply: channel vectors and pixel rows per block, rows per thread, pixels per chunk, chunks per image
+ *   [11] gepi_bwd2s: blocks per image;  [12] rows gepi_rows_prereduce leaves of their partials (0: it does not run)
+ *   [13], [14]  gepi_fin_bwd2 sums [13] x [14] partial rows per channel
+ * Returns the entry point's error code for the shape: 0, SGX_EINVAL, SGX_EUNSUPPORTED. */
+enum { SGX_GEPI_PLAN_FWD = 0, SGX_GEPI_PLAN_BWD = 1, SGX_GEPI_PLAN_STATS = 2 };
+#define SGX_GEPI_PLAN_INTS 15
+int sgx_gepi_plan(int entry, int B, int HW, int C, int flags, int pre, int dtype, int* out);
 /* y = blur3x3(x) (the generator's upscale-conv -> blur, models/CustomLayers.py:176-177, Blocks.py:63-65) with the statistics
  * pass of the LayerEpilogue that follows (:232-233 after :224-229) folded into the store: part receives the per-block partial
  * sums of a = act(y + bias[c] + nw[c]*noise[b,p]) and a^2 (y as stored), sgx_blur3x3_stats_nparts(...) blocks per image.

@@ -15,37 +15,6 @@
 #define GEPI_MIN_BLOCKS 512        // (2048 blocks were tried for the read-only reduction passes: the per-block reduction tail costs more than the extra loads in flight gain)
 #endif
 
-struct GepiGeom { int cvt, rows, chunk, nchunk; };
-// Rows per thread: 64 for the big layers (few partials), fewer for the small ones so that a launch still has
-// GEPI_MIN_BLOCKS blocks (a 4x4..64x64 layer with 64 rows per thread is a handful of blocks walking a long serial loop).
-static GepiGeom gepi_geom(int B, int HW, int C, int ve) {
-    GepiGeom g;
-    int cv = C / ve;
-    if (cv < 1) cv = 1;            // (sgx_gepi_ws_bytes sizes for both vector widths: fp32 with C = 4 has no bf16 vector, and rows divides by cvt)
-    g.cvt = cv < 256 ? cv : 256;
-    g.rows = 256 / g.cvt;
-    static const int rpt_max = [] { const char* e = getenv("SGX_GEPI_RPT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : GEPI_ROWS_PER_THREAD; }();
-    int rpt = rpt_max;
-    while (rpt > 8 && (long)B * ((HW + g.rows * rpt - 1) / (g.rows * rpt)) < GEPI_MIN_BLOCKS) rpt >>= 1;
-    g.chunk = g.rows * rpt;
-    g.nchunk = (HW + g.chunk - 1) / g.chunk;
-    return g;
-}
-
-static size_t gepi_ws_head(int B, int HW, int C) {
-    GepiGeom g4 = gepi_geom(B, HW, C, 4), g8 = gepi_geom(B, HW, C, 8);
-    int nchunk = g4.nchunk > g8.nchunk ? g4.nchunk : g8.nchunk;
-    return ((size_t)2 * B * nchunk * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float) + 255) / 256 * 256;
-}
-// behind the head: [B][7][C] floats (the short-lived apply passes' coefficient tables), then the per-block partials of gepi_bwd2s
-static size_t gepi_ws_tab(int B, int C) { return ((size_t)B * 7 * C * sizeof(float) + 255) / 256 * 256; }
-extern "C" size_t sgx_gepi_ws_bytes(int B, int HW, int C) {
-    const size_t nblk = ((size_t)HW * (C / 4) + 1023) / 1024;                     // (the fp32 vector width gives the larger count)
-    return gepi_ws_head(B, HW, C) + gepi_ws_tab(B, C) + (size_t)B * nblk * C * 2 * sizeof(double) + 256;
-}
-static float* gepi_ctab(void* ws, int B, int HW, int C) { return reinterpret_cast<float*>(static_cast<char*>(ws) + gepi_ws_head(B, HW, C)); }
-static double* gepi_part2s(void* ws, int B, int HW, int C) { return reinterpret_cast<double*>(static_cast<char*>(ws) + gepi_ws_head(B, HW, C) + gepi_ws_tab(B, C)); }
-
 // sum over 16 consecutive lanes (the finalizers give every output 16 lanes that stride over the chunk partials)
 __device__ __forceinline__ double sum16(double v) {
 #pragma unroll
@@ -552,25 +521,6 @@ __global__ __launch_bounds__(256) void gepi_rows_prereduce(const double* __restr
         out[(size_t)j * Wd + threadIdx.x] = t;
     }
 }
-// Measured alone (tools/gepi_probe.py, both backward passes + finalisers, batch 32): 1024^2 x 16 1043..1083 -> 1002 us, 512^2 x 32 531 -> 526,
-// 256^2 x 64 284 -> 319 (worse): the noise load, the coefficient table, the in-block sums and the extra pre-reduction launch eat most of what the
-// two-input stream gains in the probe (267 vs 348 us for 1.6 GB).  So: tensors of >= 800 MB only (the 1024^2 layer from batch 24 up).
-static bool gepi_bwd2s_on(int C, int VE, double tensor_bytes) {
-    static const int on = [] { const char* e = getenv("SGX_GEPI_BWD2S"); return e ? atoi(e) : 1; }();       // A/B switch; 2 = whatever the size
-    const int cv = C / VE;
-    return on != 0 && C <= 128 && cv >= 1 && cv <= 16 && (cv & (cv - 1)) == 0 && (on == 2 || tensor_bytes >= 800e6);
-}
-// partials of the short-lived backward apply pass: blocks per image
-static int gepi_bwd2s_blocks(int HW, int C, int VE) { return (int)(((size_t)HW * (C / VE) + 1023) / 1024); }
-
-// the launch of the apply pass: short-lived blocks (SGX_GEPI_APPLY1, default 1) or the long-loop kernel with the statistics finalize folded in
-// Measured alone (tools/gepi_probe.py, statistics + apply, batch 32): 1024^2 x 16: 664 -> 599 us, 512^2 x 32: 345 -> 310, 256^2 x 64: 175 -> 170,
-// 128^2 x 128: no change; batch 4 (tensors of <= 134 MB): +2..3 us for the separate finalize launch and nothing back.  So: tensors of >= 192 MB.
-static bool gepi_apply1_on(int C, double tensor_bytes) {
-    static const int on = [] { const char* e = getenv("SGX_GEPI_APPLY1"); return e ? atoi(e) : 1; }();      // 2 = whatever the size
-    // (a block's table is 24 C bytes next to 4 KB of data: the 256 / 512-channel layers keep the loop)
-    return on != 0 && C <= 128 && (on == 2 || tensor_bytes >= 192e6);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Small layers (round 6): the whole epilogue of one (image, 16-channel group) in ONE block, one launch per direction.
@@ -781,188 +731,336 @@ __global__ __launch_bounds__(NT) void gepi_small_bwd(const T* __restrict__ x, co
         o[0] = tot[vv * W2 + j]; o[1] = tot[vv * W2 + VE + j];
     }
 }
-// block shape by layer size: 256 threads x 2 pixels per lane up to 16x16 (bf16), 512 threads x 4 up to 32x32 (1024 threads x 2 caps the
-// kernel at 128 registers: the bf16 backward spilled 40 bytes); a 64x64 layer would be 16 cached vectors per lane and stays two-pass
-template <typename T> struct GsPlan {
-    static constexpr int NV = GS_CG / VecTraits<T>::VE;
-    static constexpr int MAX_HW = 4 * (512 / NV);                  // bf16: 1024, fp32: 512
-    static int pick(int HW) { return HW <= 2 * (256 / NV) ? 0 : 1; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The launch layer.  What a call launches is decided once, by gepi_fwd_plan / gepi_bwd_plan / gepi_stats_plan: every size threshold and
+// every switch is evaluated there and nowhere else.  gepi_fwd_t / gepi_bwd_t / gepi_stats_t execute a plan, each kernel instantiation from
+// one launch site, on the regions of the workspace that GepiWs lays out; sgx_gepi_plan reports the same plan without launching.
+// Switches: A/B against the paths the newer kernels replaced.
+SGX_SWITCH(gepi_rpt_env, "SGX_GEPI_RPT", 0)                        // pixel rows per thread of the two-pass kernels at most; <= 0: GEPI_ROWS_PER_THREAD
+SGX_SWITCH(gepi_small_env, "SGX_GEPI_SMALL", 1)                    // 0: the two-pass structure at every size
+SGX_SWITCH(gepi_apply1_env, "SGX_GEPI_APPLY1", 1)                  // 0: never gepi_apply1; 2: whatever the size
+SGX_SWITCH(gepi_bwd2s_env, "SGX_GEPI_BWD2S", 1)                    // 0: never gepi_bwd2s; 2: whatever the size
+SGX_SWITCH(gepi_fold_env, "SGX_GEPI_FOLD", 1)                      // 0: gepi_fin_stats / gepi_fin_bwd1 as launches of their own
+
+static int gepi_ve(int dtype) { return dtype == SGX_F32 ? 4 : 8; }
+// one body for both element types: f(T{})
+template <typename F> static int gepi_by_dtype(int dtype, F f) { return dtype == SGX_F32 ? f(float{}) : f(bf16_t{}); }
+// channel counts the block layout takes: whole 16-byte vectors, and 256 threads a multiple of the channel vectors or the other way round
+static bool gepi_channels_ok(int C, int ve) { return C % ve == 0 && ((C / ve) <= 256 ? 256 % (C / ve) == 0 : (C / ve) % 256 == 0); }
+
+struct GepiGeom { int cvt, rows, rpt, chunk, nchunk; };
+// Rows per thread: 64 for the big layers (few partials), fewer for the small ones so that a launch still has
+// GEPI_MIN_BLOCKS blocks (a 4x4..64x64 layer with 64 rows per thread is a handful of blocks walking a long serial loop).
+static GepiGeom gepi_geom(int B, int HW, int C, int ve) {
+    GepiGeom g;
+    int cv = C / ve;
+    if (cv < 1) cv = 1;            // (GepiWs sizes for both vector widths: fp32 with C = 4 has no bf16 vector, and rows divides by cvt)
+    g.cvt = cv < 256 ? cv : 256;
+    g.rows = 256 / g.cvt;
+    g.rpt = gepi_rpt_env() > 0 ? gepi_rpt_env() : GEPI_ROWS_PER_THREAD;
+    while (g.rpt > 8 && (long)B * ((HW + g.rows * g.rpt - 1) / (g.rows * g.rpt)) < GEPI_MIN_BLOCKS) g.rpt >>= 1;
+    g.chunk = g.rows * g.rpt;
+    g.nchunk = (HW + g.chunk - 1) / g.chunk;
+    return g;
+}
+
+// The workspace of one call.  Head: the per-chunk partials of the two passes -- A (statistics / backward reduction), then B (d noise-weight,
+// d bias), which follows A by the CALL's own nchunk, while the head is sized by the larger nchunk of the two vector widths -- and behind B
+// the [B][C][2] coefficient pairs of gepi_fin_bwd1.  Behind the head, 256-byte aligned: [B][7][C] floats (the short-lived apply passes'
+// coefficient tables; the forward uses 6 of the 7), then the per-block partials of gepi_bwd2s (the fp32 vector width gives the larger count).
+struct GepiWs {
+    char* base;
+    size_t part_bytes, head_bytes, tab_bytes, blk_bytes;
+    GepiWs(void* ws, int B, int HW, int C, int ve) : base(static_cast<char*>(ws)) {
+        const GepiGeom g4 = gepi_geom(B, HW, C, 4), g8 = gepi_geom(B, HW, C, 8);
+        const int nchunk = g4.nchunk > g8.nchunk ? g4.nchunk : g8.nchunk;
+        part_bytes = (size_t)B * (ve == 4 ? g4 : g8).nchunk * C * 2 * sizeof(double);
+        head_bytes = align_up((size_t)2 * B * nchunk * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float), 256);
+        tab_bytes = align_up((size_t)B * 7 * C * sizeof(float), 256);
+        blk_bytes = (size_t)B * (((size_t)HW * (C / 4) + 1023) / 1024) * C * 2 * sizeof(double);
+    }
+    size_t bytes() const { return head_bytes + tab_bytes + blk_bytes + 256; }
+    double* partA() const { return reinterpret_cast<double*>(base); }
+    double* partB() const { return reinterpret_cast<double*>(base + part_bytes); }
+    float* coef() const { return reinterpret_cast<float*>(base + 2 * part_bytes); }
+    float* ctab() const { return reinterpret_cast<float*>(base + head_bytes); }
+    double* blk_part() const { return reinterpret_cast<double*>(base + head_bytes + tab_bytes); }
+};
+extern "C" size_t sgx_gepi_ws_bytes(int B, int HW, int C) { return GepiWs(nullptr, B, HW, C, 4).bytes(); }
+
+// block shape of the one-launch kernels by layer size: 256 threads x 2 pixels per lane up to 16x16 (bf16), 512 threads x 4 up to 32x32 (1024
+// threads x 2 caps the kernel at 128 registers: the bf16 backward spilled 40 bytes); a 64x64 layer would be 16 cached vectors per lane and
+// stays two-pass
+struct GsPlan {
+    static int max_hw(int ve) { return 4 * (512 / (GS_CG / ve)); }           // MAX_HW: bf16 1024, fp32 512 pixels
+    static int pick(int HW, int ve) { return HW <= 2 * (256 / (GS_CG / ve)) ? 0 : 1; }
 };
 // which layers take the one-launch kernels (SGX_GEPI_SMALL=0: A/B against the two-pass structure)
-template <typename T> static bool gepi_small_ok(int B, int HW, int C) {
-    static const int on = [] { const char* e = getenv("SGX_GEPI_SMALL"); return e ? atoi(e) : 1; }();
+static bool gepi_small_ok(int B, int HW, int C, int ve) {
     // measured (tools/gepi_probe.py, kernel time forward / backward, two-pass -> one launch): batch 4: 4x4..16x16 18-21 / 30-34 -> 8-9 / 19-20 us,
     // 32x32 26 / 39 -> 16 / 36; batch 32: 16x16 26 / 39 -> 19 / 37, but 32x32 39 / 59 -> 60 / 125: a block reads 32 of every 128-byte line, and
     // once the layer (33 MB) no longer sits in L2 the other three quarters are fetched again by the blocks of the other channel groups
-    const long bytes = (long)B * HW * C * (long)sizeof(T);
-    return on && C % GS_CG == 0 && (long)B * (C / GS_CG) >= 64 && (HW <= GsPlan<T>::MAX_HW / 4 || (HW <= GsPlan<T>::MAX_HW && bytes <= (8L << 20)));
+    const long bytes = (long)B * HW * C * (16 / ve);
+    return gepi_small_env() && C % GS_CG == 0 && (long)B * (C / GS_CG) >= 64 &&
+           (HW <= GsPlan::max_hw(ve) / 4 || (HW <= GsPlan::max_hw(ve) && bytes <= (8L << 20)));
+}
+// the forward apply pass: short-lived blocks (SGX_GEPI_APPLY1, default 1) or the long-loop kernel with the statistics finalize folded in
+// Measured alone (tools/gepi_probe.py, statistics + apply, batch 32): 1024^2 x 16: 664 -> 599 us, 512^2 x 32: 345 -> 310, 256^2 x 64: 175 -> 170,
+// 128^2 x 128: no change; batch 4 (tensors of <= 134 MB): +2..3 us for the separate finalize launch and nothing back.  So: tensors of >= 192 MB.
+static bool gepi_apply1_on(int C, double tensor_bytes) {
+    // (a block's table is 24 C bytes next to 4 KB of data: the 256 / 512-channel layers keep the loop)
+    return gepi_apply1_env() != 0 && C <= 128 && (gepi_apply1_env() == 2 || tensor_bytes >= 192e6);
+}
+// the backward apply pass as short-lived blocks (SGX_GEPI_BWD2S, default 1)
+// Measured alone (tools/gepi_probe.py, both backward passes + finalisers, batch 32): 1024^2 x 16 1043..1083 -> 1002 us, 512^2 x 32 531 -> 526,
+// 256^2 x 64 284 -> 319 (worse): the noise load, the coefficient table, the in-block sums and the extra pre-reduction launch eat most of what the
+// two-input stream gains in the probe (267 vs 348 us for 1.6 GB).  So: tensors of >= 800 MB only (the 1024^2 layer from batch 24 up).
+static bool gepi_bwd2s_on(int C, int ve, double tensor_bytes) {
+    const int cv = C / ve;
+    return gepi_bwd2s_env() != 0 && C <= 128 && cv >= 1 && cv <= 16 && (cv & (cv - 1)) == 0 && (gepi_bwd2s_env() == 2 || tensor_bytes >= 800e6);
+}
+
+// Everything one call will do (sgx_gepi_plan in include/sgx.h spells the same fields out for a caller).
+enum { GEPI_FIN_NONE = 0, GEPI_FIN_LAUNCH = 1, GEPI_FIN_TABLE = 2, GEPI_FIN_FOLDED = 3 };
+enum { GEPI_APPLY_NONE = 0, GEPI_APPLY_LOOP = 1, GEPI_APPLY_SHORT = 2 };
+struct GepiPlan {
+    GepiGeom g;              // of the two-pass kernels
+    int small = 0;           // the whole direction in one launch: 0 no, 1 gepi_small_*<T, 256, 2>, 2 <T, 512, 4> (+ gepi_fin_bwd2 in the backward)
+    int pass = 0;            // the reduction pass runs: gepi_pass<T, 0> (forward, statistics), gepi_pass<T, 1> (backward)
+    int from_pre = 0;        // the finalize reads the producer's partials, not the pass's
+    int fin = GEPI_FIN_NONE; // gepi_fin_stats / gepi_fin_bwd1: a launch, the same also writing the coefficient table, or folded into the apply kernel
+    int apply = GEPI_APPLY_NONE;   // LOOP: gepi_apply / gepi_pass<T, 2>;  SHORT: gepi_apply1 / gepi_bwd2s
+    int nt = 0;              // the apply kernel's accesses carry the nontemporal hint (the short-lived kernels: always)
+    int nblk = 0, pre_rows = 0;    // gepi_bwd2s: blocks per image, rows gepi_rows_prereduce leaves (0: it does not run)
+    int fin2_B = 0, fin2_n = 0;    // gepi_fin_bwd2 sums fin2_B * fin2_n partial rows
+};
+static double gepi_tensor_bytes(int B, int HW, int C, int ve) { return (double)(16 / ve) * B * HW * C; }
+
+static GepiPlan gepi_stats_plan(int B, int HW, int C, int ve, int flags, bool pre) {
+    GepiPlan p;
+    p.g = gepi_geom(B, HW, C, ve);
+    p.pass = (flags & SGX_EPI_NORM) && !pre;
+    p.from_pre = pre;
+    p.fin = GEPI_FIN_LAUNCH;
+    return p;
+}
+static GepiPlan gepi_fwd_plan(int B, int HW, int C, int ve, int flags, bool pre) {
+    const bool norm = flags & SGX_EPI_NORM;
+    const bool apply1 = gepi_apply1_on(C, gepi_tensor_bytes(B, HW, C, ve));
+    GepiPlan p;
+    p.g = gepi_geom(B, HW, C, ve);
+    // pre: the statistics pass already happened in the kernel that PRODUCED x (sgx_blur3x3_stats / the convolution's store epilogue):
+    // partial (sum a, sum a^2) pairs per (image, channel), same layout as gepi_pass<T, 0> writes
+    p.from_pre = norm && pre;
+    if (!p.from_pre && gepi_small_ok(B, HW, C, ve)) {              // (with or without the normalisation: one launch)
+        p.small = 1 + GsPlan::pick(HW, ve);
+        return p;
+    }
+    p.pass = norm && !pre;
+    p.apply = apply1 ? GEPI_APPLY_SHORT : GEPI_APPLY_LOOP;
+    p.nt = apply1;
+    // the statistics' finalize (mean / rstd from the per-chunk partials) rides in the apply pass: every block sums the partials of its image
+    // itself (SGX_GEPI_FOLD=0: the separate gepi_fin_stats launch, A/B) -- but for gepi_apply1, which reads the table gepi_fin_stats writes,
+    // and for the producer's partials
+    p.fin = apply1 ? GEPI_FIN_TABLE : (p.from_pre || !gepi_fold_env() ? GEPI_FIN_LAUNCH : GEPI_FIN_FOLDED);
+    return p;
+}
+static GepiPlan gepi_bwd_plan(int B, int HW, int C, int ve) {
+    const double nb = gepi_tensor_bytes(B, HW, C, ve);
+    GepiPlan p;
+    p.g = gepi_geom(B, HW, C, ve);
+    p.fin2_B = B;
+    if (gepi_small_ok(B, HW, C, ve)) {
+        p.small = 1 + GsPlan::pick(HW, ve);
+        p.fin2_n = 1;
+        return p;
+    }
+    p.pass = 1;
+    if (gepi_bwd2s_on(C, ve, nb)) {
+        p.fin = GEPI_FIN_TABLE;
+        p.apply = GEPI_APPLY_SHORT;
+        p.nt = 1;
+        p.nblk = (int)(((size_t)HW * (C / ve) + 1023) / 1024);
+        // B * nblk partial rows -> <= 256 (into the head's B region, sized for B * nchunk >= 256 rows at these tensor sizes) -> the two gradients
+        const int K = B * p.nblk, NB = K < 256 ? K : 256;
+        const bool pre = (size_t)NB <= (size_t)B * p.g.nchunk && 2 * C <= 256;
+        p.pre_rows = pre ? NB : 0;
+        p.fin2_B = pre ? 1 : B;
+        p.fin2_n = pre ? NB : p.nblk;
+        return p;
+    }
+    // gepi_fin_bwd1's work (dstyle, the statistics-gradient coefficients) in the prologue of the apply pass (SGX_GEPI_FOLD=0: its own launch)
+    p.fin = gepi_fold_env() ? GEPI_FIN_FOLDED : GEPI_FIN_LAUNCH;
+    p.apply = GEPI_APPLY_LOOP;
+    p.nt = gepi_fold_env() && sgx_nt_for(nb);
+    p.fin2_n = p.g.nchunk;
+    return p;
+}
+
+// the operands of a call, as the entry points take them (what an entry point does not have is NULL)
+struct GepiArgs {
+    const void *x, *dy;
+    void* out;                                                     // y / dx
+    const float *bias, *noise, *nw, *style;
+    float *mean, *rstd;                                            // written by the forward and the statistics, read by the backward
+    float *dstyle, *dnw, *dbias;
+    const double* pre_part;
+    int pre_npart, B, HW, C, act, norm;
+    hipStream_t st;
+    double bytes(int ve) const { return gepi_tensor_bytes(B, HW, C, ve); }
+};
+
+template <typename T>
+static int gepi_launch_pass0(const GepiArgs& a, const GepiGeom& g, double* part) {
+    constexpr int VE = VecTraits<T>::VE;
+    SGX_NOTE(0.0, a.bytes(VE), "gepi_stats B%d HW%d C%d", a.B, a.HW, a.C);
+    hipLaunchKernelGGL((gepi_pass<T, 0>), dim3(g.nchunk, a.B), dim3(256), 256 * 2 * VE * sizeof(double), a.st, (const T*)a.x,
+                       (const T*)nullptr, (T*)nullptr, a.bias, a.noise, a.nw, a.style, (const float*)a.mean, (const float*)a.rstd,
+                       (const float*)nullptr, part, a.HW, a.C, g.cvt, g.rows, g.chunk, a.act, (const double*)nullptr, 0, 0, (float*)nullptr);
+    SGX_LAUNCH_CHECK("gepi_stats");
+    return 0;
+}
+// mean / rstd from npart partial pairs per (image, channel); tab: also the coefficient table of gepi_apply1 (NULL: none)
+static int gepi_launch_fin_stats(const GepiArgs& a, const double* part, int npart, float* tab) {
+    hipLaunchKernelGGL(gepi_fin_stats, dim3((a.B * a.C + 15) / 16), dim3(256), 0, a.st, part, a.mean, a.rstd, a.B, a.C, npart, a.HW, a.norm, tab,
+                       tab ? a.bias : nullptr, tab ? a.nw : nullptr, tab ? a.style : nullptr);
+    SGX_LAUNCH_CHECK("gepi_fin_stats");
+    return 0;
 }
 
 template <typename T>
-static int gepi_fwd_t(const void* x, const float* bias, const float* noise, const float* nw, const float* style, void* y,
-                      float* mean, float* rstd, void* ws, const double* pre_part, int pre_npart, int B, int HW, int C, int flags,
-                      hipStream_t st) {
-    const int act = (flags & SGX_EPI_ACT) ? SGX_ACT_LRELU : SGX_ACT_NONE, norm = (flags & SGX_EPI_NORM) ? 1 : 0;
+static int gepi_fwd_t(const GepiArgs& a, const GepiPlan& p, const GepiWs& w) {
     constexpr int VE = VecTraits<T>::VE;
-    GepiGeom g = gepi_geom(B, HW, C, VE);
-    double* part = static_cast<double*>(ws);
-    float* ctab = gepi_ctab(ws, B, HW, C);                         // gepi_apply1's coefficient tables, behind the partials of both directions
-    const double nb = (double)sizeof(T) * B * HW * C;
-    if (norm && pre_part) {
-        // the statistics pass already happened in the kernel that PRODUCED x (sgx_blur3x3_stats / the convolution's store
-        // epilogue): pre_npart partial (sum a, sum a^2) pairs per (image, channel), same layout as gepi_pass<T, 0> writes
-        if (gepi_apply1_on(C, nb)) {
-            hipLaunchKernelGGL(gepi_fin_stats, dim3((B * C + 15) / 16), dim3(256), 0, st, pre_part, mean, rstd, B, C, pre_npart, HW, norm, ctab, bias, nw, style);
-            SGX_LAUNCH_CHECK("gepi_fin_stats");
-            SGX_NOTE(0.0, 2.0 * nb, "gepi_apply B%d HW%d C%d", B, HW, C);
-            hipLaunchKernelGGL(gepi_apply1<T>, dim3((unsigned)(((size_t)HW * (C / VE) + 255) / 256), B), dim3(256), 6 * C * sizeof(float), st, (const T*)x, noise,
-                               (const float*)ctab, (T*)y, HW, C, act);
-            SGX_LAUNCH_CHECK("gepi_apply1");
-            return 0;
-        }
-        hipLaunchKernelGGL(gepi_fin_stats, dim3((B * C + 15) / 16), dim3(256), 0, st, pre_part, mean, rstd, B, C, pre_npart, HW, norm, (float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_fin_stats");
-        SGX_NOTE(0.0, 2.0 * nb, "gepi_apply B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL(gepi_apply<T>, dim3(g.nchunk, B), dim3(256), 0, st, (const T*)x, bias, noise, nw, style, mean, rstd,
-                           (T*)y, HW, C, g.cvt, g.rows, g.chunk, act, (const double*)nullptr, 0, 0, (float*)nullptr, (float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_apply");
-        return 0;
-    }
-    if (gepi_small_ok<T>(B, HW, C)) {                   // (with or without the normalisation: one launch)
-        SGX_NOTE(0.0, 2.0 * nb, "gepi_fwd1 B%d HW%d C%d", B, HW, C);
-        const dim3 grid(C / GS_CG, B);
-        switch (GsPlan<T>::pick(HW)) {
-            case 0: hipLaunchKernelGGL((gepi_small_fwd<T, 256, 2>), grid, dim3(256), 0, st, (const T*)x, bias, noise, nw, style, (T*)y, mean, rstd, HW, C, act, norm); break;
-            default: hipLaunchKernelGGL((gepi_small_fwd<T, 512, 4>), grid, dim3(512), 0, st, (const T*)x, bias, noise, nw, style, (T*)y, mean, rstd, HW, C, act, norm);
-        }
+    const GepiGeom& g = p.g;
+    const T* x = (const T*)a.x;
+    T* y = (T*)a.out;
+    if (p.small) {
+        SGX_NOTE(0.0, 2.0 * a.bytes(VE), "gepi_fwd1 B%d HW%d C%d", a.B, a.HW, a.C);
+        const dim3 grid(a.C / GS_CG, a.B);
+        if (p.small == 1)
+            hipLaunchKernelGGL((gepi_small_fwd<T, 256, 2>), grid, dim3(256), 0, a.st, x, a.bias, a.noise, a.nw, a.style, y, a.mean, a.rstd, a.HW, a.C, a.act, a.norm);
+        else
+            hipLaunchKernelGGL((gepi_small_fwd<T, 512, 4>), grid, dim3(512), 0, a.st, x, a.bias, a.noise, a.nw, a.style, y, a.mean, a.rstd, a.HW, a.C, a.act, a.norm);
         SGX_LAUNCH_CHECK("gepi_small_fwd");
         return 0;
     }
-    if (norm) {
-        SGX_NOTE(0.0, nb, "gepi_stats B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL((gepi_pass<T, 0>), dim3(g.nchunk, B), dim3(256), 256 * 2 * VE * sizeof(double), st, (const T*)x,
-                           (const T*)nullptr, (T*)nullptr, bias, noise, nw, style, mean, rstd, (const float*)nullptr, part, HW, C,
-                           g.cvt, g.rows, g.chunk, act, (const double*)nullptr, 0, 0, (float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_stats");
-    }
-    // the statistics' finalize (mean / rstd from the per-chunk partials) rides in the apply pass: every block sums the partials of
-    // its image itself (SGX_GEPI_FOLD=0: the separate gepi_fin_stats launch, A/B)
-    static const int fold = [] { const char* e = getenv("SGX_GEPI_FOLD"); return e ? atoi(e) : 1; }();
-    if (gepi_apply1_on(C, nb)) {
-        hipLaunchKernelGGL(gepi_fin_stats, dim3((B * C + 15) / 16), dim3(256), 0, st, (const double*)part, mean, rstd, B, C, g.nchunk, HW, norm, ctab, bias, nw, style);
-        SGX_LAUNCH_CHECK("gepi_fin_stats");
-        SGX_NOTE(0.0, 2.0 * nb, "gepi_apply B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL(gepi_apply1<T>, dim3((unsigned)(((size_t)HW * (C / VE) + 255) / 256), B), dim3(256), 6 * C * sizeof(float), st, (const T*)x, noise,
-                           (const float*)ctab, (T*)y, HW, C, act);
+    int rc = p.pass ? gepi_launch_pass0<T>(a, g, w.partA()) : 0;
+    if (rc) return rc;
+    const double* part = p.from_pre ? a.pre_part : w.partA();
+    const int npart = p.from_pre ? a.pre_npart : g.nchunk;
+    if (p.fin == GEPI_FIN_LAUNCH || p.fin == GEPI_FIN_TABLE) rc = gepi_launch_fin_stats(a, part, npart, p.fin == GEPI_FIN_TABLE ? w.ctab() : nullptr);
+    if (rc) return rc;
+    SGX_NOTE(0.0, 2.0 * a.bytes(VE), "gepi_apply B%d HW%d C%d", a.B, a.HW, a.C);
+    if (p.apply == GEPI_APPLY_SHORT) {
+        hipLaunchKernelGGL(gepi_apply1<T>, dim3((unsigned)(((size_t)a.HW * (a.C / VE) + 255) / 256), a.B), dim3(256), 6 * a.C * sizeof(float), a.st, x, a.noise,
+                           (const float*)w.ctab(), y, a.HW, a.C, a.act);
         SGX_LAUNCH_CHECK("gepi_apply1");
         return 0;
     }
-    if (fold) {
-        SGX_NOTE(0.0, 2.0 * nb, "gepi_apply B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL(gepi_apply<T>, dim3(g.nchunk, B), dim3(256), 512 * sizeof(double) + 2 * C * sizeof(float), st, (const T*)x, bias, noise,
-                           nw, style, mean, rstd, (T*)y, HW, C, g.cvt, g.rows, g.chunk, act, (const double*)part, norm ? g.nchunk : 0, norm, mean, rstd);
-        SGX_LAUNCH_CHECK("gepi_apply");
-        return 0;
-    }
-    hipLaunchKernelGGL(gepi_fin_stats, dim3((B * C + 15) / 16), dim3(256), 0, st, (const double*)part, mean, rstd, B, C, g.nchunk, HW, norm, (float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    SGX_LAUNCH_CHECK("gepi_fin_stats");
-    SGX_NOTE(0.0, 2.0 * nb, "gepi_apply B%d HW%d C%d", B, HW, C);
-    hipLaunchKernelGGL(gepi_apply<T>, dim3(g.nchunk, B), dim3(256), 0, st, (const T*)x, bias, noise, nw, style, mean, rstd,
-                       (T*)y, HW, C, g.cvt, g.rows, g.chunk, act, (const double*)nullptr, 0, 0, (float*)nullptr, (float*)nullptr);
+    const bool fold = p.fin == GEPI_FIN_FOLDED;                    // the kernel finalizes the partials itself and writes mean / rstd out
+    hipLaunchKernelGGL(gepi_apply<T>, dim3(g.nchunk, a.B), dim3(256), fold ? 512 * sizeof(double) + 2 * a.C * sizeof(float) : 0, a.st, x, a.bias, a.noise,
+                       a.nw, a.style, (const float*)a.mean, (const float*)a.rstd, y, a.HW, a.C, g.cvt, g.rows, g.chunk, a.act,
+                       fold ? part : (const double*)nullptr, fold && a.norm ? npart : 0, fold ? a.norm : 0, fold ? a.mean : nullptr, fold ? a.rstd : nullptr);
     SGX_LAUNCH_CHECK("gepi_apply");
     return 0;
 }
 
+// The statistics half of sgx_gepi_fwd alone: mean / rstd of a = act(x + bias + nw * noise) per (image, channel), from the pass
+// over x or from the partials the producer of x already wrote -- for a consumer that applies the normalisation and style itself
+// (sgx_rgb_out_epi: the LAST epilogue of the generator, whose output only feeds to_rgb).
 template <typename T>
-static int gepi_bwd_t(const void* dy, const void* x, const float* bias, const float* noise, const float* nw,
-                      const float* style, const float* mean, const float* rstd, void* dx, float* dstyle, float* dnw,
-                      float* dbias, void* ws, int B, int HW, int C, int flags, hipStream_t st) {
+static int gepi_stats_t(const GepiArgs& a, const GepiPlan& p, const GepiWs& w) {
+    const int rc = p.pass ? gepi_launch_pass0<T>(a, p.g, w.partA()) : 0;
+    if (rc) return rc;
+    return gepi_launch_fin_stats(a, p.from_pre ? a.pre_part : w.partA(), p.from_pre ? a.pre_npart : p.g.nchunk, nullptr);
+}
+
+template <typename T>
+static int gepi_bwd_t(const GepiArgs& a, const GepiPlan& p, const GepiWs& w) {
     constexpr int VE = VecTraits<T>::VE;
-    const int act = (flags & SGX_EPI_ACT) ? SGX_ACT_LRELU : SGX_ACT_NONE, norm = (flags & SGX_EPI_NORM) ? 1 : 0;
-    GepiGeom g = gepi_geom(B, HW, C, VE);
-    double* partA = static_cast<double*>(ws);
-    double* partB = partA + (size_t)B * g.nchunk * C * 2;
-    float* coef = reinterpret_cast<float*>(partB + (size_t)B * g.nchunk * C * 2);
+    const GepiGeom& g = p.g;
+    const T *x = (const T*)a.x, *dy = (const T*)a.dy;
+    T* dx = (T*)a.out;
+    const float *mean = a.mean, *rstd = a.rstd;
+    const int B = a.B, HW = a.HW, C = a.C;
     const size_t shb = 256 * 2 * VE * sizeof(double);
-    const double nb = (double)sizeof(T) * B * HW * C;
-    if (gepi_small_ok<T>(B, HW, C)) {
-        SGX_NOTE(0.0, 3.0 * nb, "gepi_bwd B%d HW%d C%d", B, HW, C);
+    const double* fin2_src = w.partB();                            // what gepi_fin_bwd2 sums: the apply pass's partials, but for gepi_bwd2s
+    if (p.small) {
+        SGX_NOTE(0.0, 3.0 * a.bytes(VE), "gepi_bwd B%d HW%d C%d", B, HW, C);
         const dim3 grid(C / GS_CG, B);
-        switch (GsPlan<T>::pick(HW)) {
-            case 0: hipLaunchKernelGGL((gepi_small_bwd<T, 256, 2>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, (T*)dx, bias, noise, nw, style, mean, rstd, dstyle, partB, HW, C, act, norm); break;
-            default: hipLaunchKernelGGL((gepi_small_bwd<T, 512, 4>), grid, dim3(512), 0, st, (const T*)x, (const T*)dy, (T*)dx, bias, noise, nw, style, mean, rstd, dstyle, partB, HW, C, act, norm);
-        }
-        SGX_LAUNCH_CHECK("gepi_small_bwd");
-        hipLaunchKernelGGL(gepi_fin_bwd2, dim3((C + 3) / 4), dim3(256), 0, st, partB, dnw, dbias, B, C, 1);
-        SGX_LAUNCH_CHECK("gepi_fin_bwd2");
-        return 0;
-    }
-    SGX_NOTE(0.0, 2.0 * nb, "gepi_bwd1 B%d HW%d C%d", B, HW, C);
-    hipLaunchKernelGGL((gepi_pass<T, 1>), dim3(g.nchunk, B), dim3(256), shb, st, (const T*)x, (const T*)dy, (T*)nullptr, bias,
-                       noise, nw, style, mean, rstd, (const float*)nullptr, partA, HW, C, g.cvt, g.rows, g.chunk, act,
-                       (const double*)nullptr, 0, 0, (float*)nullptr);
-    SGX_LAUNCH_CHECK("gepi_bwd1");
-    static const int fold = [] { const char* e = getenv("SGX_GEPI_FOLD"); return e ? atoi(e) : 1; }();
-    if (gepi_bwd2s_on(C, VE, nb)) {
-        float* ctab = gepi_ctab(ws, B, HW, C);
-        double* part2 = gepi_part2s(ws, B, HW, C);
-        const int nblk = gepi_bwd2s_blocks(HW, C, VE), cv = C / VE;
-        hipLaunchKernelGGL(gepi_fin_bwd1, dim3((B * C + 15) / 16), dim3(256), 0, st, (const double*)partA, style, dstyle, coef, B, C, g.nchunk, HW, norm, ctab, bias, nw,
-                           mean, rstd);
-        SGX_LAUNCH_CHECK("gepi_fin_bwd1");
-        SGX_NOTE(0.0, 3.0 * nb, "gepi_bwd2 B%d HW%d C%d", B, HW, C);
-        const size_t shs = (size_t)(7 * C + 2) * sizeof(float) + (size_t)16 * cv * 2 * VE * sizeof(double);
-        hipLaunchKernelGGL(gepi_bwd2s<T>, dim3((unsigned)nblk, B), dim3(256), shs, st, (const T*)x, (const T*)dy, (T*)dx, noise, (const float*)ctab, part2, HW, C, act);
-        SGX_LAUNCH_CHECK("gepi_bwd2s");
-        // B * nblk partial rows -> <= 256 (into the head's partB region, sized for B * nchunk >= 256 rows at these tensor sizes) -> the two gradients
-        const int K = B * nblk, NB = K < 256 ? K : 256;
-        if ((size_t)NB <= (size_t)B * g.nchunk && 2 * C <= 256) {
-            hipLaunchKernelGGL(gepi_rows_prereduce, dim3(NB), dim3(256), 256 * sizeof(double), st, (const double*)part2, partB, K, 2 * C);
-            SGX_LAUNCH_CHECK("gepi_rows_prereduce");
-            hipLaunchKernelGGL(gepi_fin_bwd2, dim3((C + 3) / 4), dim3(256), 0, st, (const double*)partB, dnw, dbias, 1, C, NB);
-        } else {
-            hipLaunchKernelGGL(gepi_fin_bwd2, dim3((C + 3) / 4), dim3(256), 0, st, (const double*)part2, dnw, dbias, B, C, nblk);
-        }
-        SGX_LAUNCH_CHECK("gepi_fin_bwd2");
-        return 0;
-    }
-    if (fold) {          // gepi_fin_bwd1's work (dstyle, the statistics-gradient coefficients) in the prologue of the apply pass
-        SGX_NOTE(0.0, 3.0 * nb, "gepi_bwd2 B%d HW%d C%d", B, HW, C);
-        if (sgx_nt_for(nb))
-            hipLaunchKernelGGL((gepi_pass<T, 2, true>), dim3(g.nchunk, B), dim3(256), shb + 2 * C * sizeof(float), st, (const T*)x, (const T*)dy, (T*)dx, bias,
-                               noise, nw, style, mean, rstd, (const float*)nullptr, partB, HW, C, g.cvt, g.rows, g.chunk, act,
-                               (const double*)partA, g.nchunk, norm, dstyle);
+        if (p.small == 1)
+            hipLaunchKernelGGL((gepi_small_bwd<T, 256, 2>), grid, dim3(256), 0, a.st, x, dy, dx, a.bias, a.noise, a.nw, a.style, mean, rstd, a.dstyle, w.partB(), HW, C, a.act, a.norm);
         else
-        hipLaunchKernelGGL((gepi_pass<T, 2>), dim3(g.nchunk, B), dim3(256), shb + 2 * C * sizeof(float), st, (const T*)x, (const T*)dy, (T*)dx, bias,
-                           noise, nw, style, mean, rstd, (const float*)nullptr, partB, HW, C, g.cvt, g.rows, g.chunk, act,
-                           (const double*)partA, g.nchunk, norm, dstyle);
-        SGX_LAUNCH_CHECK("gepi_bwd2");
+            hipLaunchKernelGGL((gepi_small_bwd<T, 512, 4>), grid, dim3(512), 0, a.st, x, dy, dx, a.bias, a.noise, a.nw, a.style, mean, rstd, a.dstyle, w.partB(), HW, C, a.act, a.norm);
+        SGX_LAUNCH_CHECK("gepi_small_bwd");
     } else {
-        hipLaunchKernelGGL(gepi_fin_bwd1, dim3((B * C + 15) / 16), dim3(256), 0, st, (const double*)partA, style, dstyle, coef, B, C, g.nchunk, HW, norm, (float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_fin_bwd1");
-        SGX_NOTE(0.0, 3.0 * nb, "gepi_bwd2 B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL((gepi_pass<T, 2>), dim3(g.nchunk, B), dim3(256), shb, st, (const T*)x, (const T*)dy, (T*)dx, bias, noise,
-                           nw, style, mean, rstd, (const float*)coef, partB, HW, C, g.cvt, g.rows, g.chunk, act,
-                           (const double*)nullptr, 0, 0, (float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_bwd2");
+        SGX_NOTE(0.0, 2.0 * a.bytes(VE), "gepi_bwd1 B%d HW%d C%d", B, HW, C);
+        hipLaunchKernelGGL((gepi_pass<T, 1>), dim3(g.nchunk, B), dim3(256), shb, a.st, x, dy, (T*)nullptr, a.bias, a.noise, a.nw, a.style, mean, rstd,
+                           (const float*)nullptr, w.partA(), HW, C, g.cvt, g.rows, g.chunk, a.act, (const double*)nullptr, 0, 0, (float*)nullptr);
+        SGX_LAUNCH_CHECK("gepi_bwd1");
+        const bool fold = p.fin == GEPI_FIN_FOLDED, tab = p.fin == GEPI_FIN_TABLE;
+        if (!fold) {                                               // dstyle and the coefficient pairs (tab: and gepi_bwd2s' coefficient table)
+            hipLaunchKernelGGL(gepi_fin_bwd1, dim3((B * C + 15) / 16), dim3(256), 0, a.st, (const double*)w.partA(), a.style, a.dstyle, w.coef(), B, C, g.nchunk, HW,
+                               a.norm, tab ? w.ctab() : nullptr, tab ? a.bias : nullptr, tab ? a.nw : nullptr, tab ? mean : nullptr, tab ? rstd : nullptr);
+            SGX_LAUNCH_CHECK("gepi_fin_bwd1");
+        }
+        SGX_NOTE(0.0, 3.0 * a.bytes(VE), "gepi_bwd2 B%d HW%d C%d", B, HW, C);
+        if (p.apply == GEPI_APPLY_SHORT) {
+            const size_t shs = (size_t)(7 * C + 2) * sizeof(float) + (size_t)16 * (C / VE) * 2 * VE * sizeof(double);
+            hipLaunchKernelGGL(gepi_bwd2s<T>, dim3((unsigned)p.nblk, B), dim3(256), shs, a.st, x, dy, dx, a.noise, (const float*)w.ctab(), w.blk_part(), HW, C, a.act);
+            SGX_LAUNCH_CHECK("gepi_bwd2s");
+            fin2_src = w.blk_part();
+            if (p.pre_rows) {
+                hipLaunchKernelGGL(gepi_rows_prereduce, dim3(p.pre_rows), dim3(256), 256 * sizeof(double), a.st, (const double*)w.blk_part(), w.partB(), B * p.nblk, 2 * C);
+                SGX_LAUNCH_CHECK("gepi_rows_prereduce");
+                fin2_src = w.partB();
+            }
+        } else {
+            // folded: the kernel sums pass 1's partials itself (dstyle, the two coefficients); else it reads the pairs gepi_fin_bwd1 wrote
+            const size_t lds = shb + (fold ? 2 * C * sizeof(float) : 0);
+            const float* coef = fold ? nullptr : w.coef();
+            const double* fpart = fold ? w.partA() : nullptr;
+            const int fn = fold ? g.nchunk : 0, fnorm = fold ? a.norm : 0;
+            float* dstyle = fold ? a.dstyle : nullptr;
+            if (p.nt)
+                hipLaunchKernelGGL((gepi_pass<T, 2, true>), dim3(g.nchunk, B), dim3(256), lds, a.st, x, dy, dx, a.bias, a.noise, a.nw, a.style, mean, rstd, coef,
+                                   w.partB(), HW, C, g.cvt, g.rows, g.chunk, a.act, fpart, fn, fnorm, dstyle);
+            else
+                hipLaunchKernelGGL((gepi_pass<T, 2>), dim3(g.nchunk, B), dim3(256), lds, a.st, x, dy, dx, a.bias, a.noise, a.nw, a.style, mean, rstd, coef,
+                                   w.partB(), HW, C, g.cvt, g.rows, g.chunk, a.act, fpart, fn, fnorm, dstyle);
+            SGX_LAUNCH_CHECK("gepi_bwd2");
+        }
     }
-    hipLaunchKernelGGL(gepi_fin_bwd2, dim3((C + 3) / 4), dim3(256), 0, st, partB, dnw, dbias, B, C, g.nchunk);
+    hipLaunchKernelGGL(gepi_fin_bwd2, dim3((C + 3) / 4), dim3(256), 0, a.st, fin2_src, a.dnw, a.dbias, p.fin2_B, C, p.fin2_n);
     SGX_LAUNCH_CHECK("gepi_fin_bwd2");
     return 0;
 }
 
+// ws_bytes: what the caller holds (sgx_gepi_plan: taken as sufficient)
 static int gepi_check(int B, int HW, int C, int dtype, size_t ws_bytes) {
-    const int ve = dtype == SGX_F32 ? 4 : 8;
     SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "gepi: bad dtype");
-    SGX_REQUIRE(C % ve == 0, SGX_EUNSUPPORTED, "gepi: C=%d", C);
-    const int cv = C / ve;
-    SGX_REQUIRE(cv <= 256 ? (256 % cv == 0) : (cv % 256 == 0), SGX_EUNSUPPORTED, "gepi: C=%d", C);
+    SGX_REQUIRE(gepi_channels_ok(C, gepi_ve(dtype)), SGX_EUNSUPPORTED, "gepi: C=%d", C);
     SGX_REQUIRE(ws_bytes >= sgx_gepi_ws_bytes(B, HW, C), SGX_EWORKSPACE, "gepi: workspace %zu < %zu", ws_bytes,
                 sgx_gepi_ws_bytes(B, HW, C));
     return 0;
+}
+
+static GepiPlan gepi_plan(int entry, int B, int HW, int C, int ve, int flags, bool pre) {
+    return entry == SGX_GEPI_PLAN_FWD ? gepi_fwd_plan(B, HW, C, ve, flags, pre)
+         : entry == SGX_GEPI_PLAN_BWD ? gepi_bwd_plan(B, HW, C, ve) : gepi_stats_plan(B, HW, C, ve, flags, pre);
+}
+// the three entry points behind their checks: the plan, the workspace view, and the runner in the call's element type
+static int gepi_run(int entry, GepiArgs a, int flags, int dtype, void* ws) {
+    a.act = (flags & SGX_EPI_ACT) ? SGX_ACT_LRELU : SGX_ACT_NONE;
+    a.norm = (flags & SGX_EPI_NORM) ? 1 : 0;
+    const int ve = gepi_ve(dtype);
+    const GepiPlan p = gepi_plan(entry, a.B, a.HW, a.C, ve, flags, a.pre_part != nullptr);
+    const GepiWs w(ws, a.B, a.HW, a.C, ve);
+    return gepi_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return entry == SGX_GEPI_PLAN_FWD ? gepi_fwd_t<T>(a, p, w) : entry == SGX_GEPI_PLAN_BWD ? gepi_bwd_t<T>(a, p, w) : gepi_stats_t<T>(a, p, w);
+    });
 }
 
 extern "C" int sgx_gepi_fwd(const void* x, const float* bias, const float* noise, const float* nw, const float* style, void* y,
@@ -971,41 +1069,40 @@ extern "C" int sgx_gepi_fwd(const void* x, const float* bias, const float* noise
     int rc = gepi_check(B, HW, C, dtype, ws_bytes);
     if (rc) return rc;
     SGX_REQUIRE(!pre_part || pre_npart > 0, SGX_EINVAL, "gepi_fwd: %d producer partials", pre_npart);
-    if (dtype == SGX_F32)
-        return gepi_fwd_t<float>(x, bias, noise, nw, style, y, mean, rstd, ws, pre_part, pre_npart, B, HW, C, flags, (hipStream_t)stream);
-    return gepi_fwd_t<bf16_t>(x, bias, noise, nw, style, y, mean, rstd, ws, pre_part, pre_npart, B, HW, C, flags, (hipStream_t)stream);
+    return gepi_run(SGX_GEPI_PLAN_FWD, {x, nullptr, y, bias, noise, nw, style, mean, rstd, nullptr, nullptr, nullptr, pre_part, pre_npart, B, HW, C, 0, 0,
+                                        (hipStream_t)stream}, flags, dtype, ws);
 }
 
-// The statistics half of sgx_gepi_fwd alone: mean / rstd of a = act(x + bias + nw * noise) per (image, channel), from the pass
-// over x or from the partials the producer of x already wrote -- for a consumer that applies the normalisation and style itself
-// (sgx_rgb_out_epi: the LAST epilogue of the generator, whose output only feeds to_rgb).
-template <typename T>
-static int gepi_stats_t(const void* x, const float* bias, const float* noise, const float* nw, float* mean, float* rstd, void* ws,
-                        const double* pre_part, int pre_npart, int B, int HW, int C, int flags, hipStream_t st) {
-    const int act = (flags & SGX_EPI_ACT) ? SGX_ACT_LRELU : SGX_ACT_NONE, norm = (flags & SGX_EPI_NORM) ? 1 : 0;
-    constexpr int VE = VecTraits<T>::VE;
-    GepiGeom g = gepi_geom(B, HW, C, VE);
-    double* part = static_cast<double*>(ws);
-    if (norm && !pre_part) {
-        SGX_NOTE(0.0, (double)sizeof(T) * B * HW * C, "gepi_stats B%d HW%d C%d", B, HW, C);
-        hipLaunchKernelGGL((gepi_pass<T, 0>), dim3(g.nchunk, B), dim3(256), 256 * 2 * VE * sizeof(double), st, (const T*)x,
-                           (const T*)nullptr, (T*)nullptr, bias, noise, nw, (const float*)nullptr, mean, rstd, (const float*)nullptr, part, HW, C,
-                           g.cvt, g.rows, g.chunk, act, (const double*)nullptr, 0, 0, (float*)nullptr);
-        SGX_LAUNCH_CHECK("gepi_stats");
-    }
-    hipLaunchKernelGGL(gepi_fin_stats, dim3((B * C + 15) / 16), dim3(256), 0, st, pre_part ? pre_part : (const double*)part, mean, rstd, B, C,
-                       pre_part ? pre_npart : g.nchunk, HW, norm, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    SGX_LAUNCH_CHECK("gepi_fin_stats");
-    return 0;
+extern "C" int sgx_gepi_bwd(const void* dy, const void* x, const float* bias, const float* noise, const float* nw,
+                            const float* style, const float* mean, const float* rstd, void* dx, float* dstyle, float* dnw,
+                            float* dbias, void* ws, size_t ws_bytes, int B, int HW, int C, int flags, int dtype, void* stream) {
+    int rc = gepi_check(B, HW, C, dtype, ws_bytes);
+    if (rc) return rc;
+    // (mean / rstd: the backward only reads them)
+    return gepi_run(SGX_GEPI_PLAN_BWD, {x, dy, dx, bias, noise, nw, style, const_cast<float*>(mean), const_cast<float*>(rstd), dstyle, dnw, dbias, nullptr, 0,
+                                        B, HW, C, 0, 0, (hipStream_t)stream}, flags, dtype, ws);
 }
+
 extern "C" int sgx_gepi_stats(const void* x, const float* bias, const float* noise, const float* nw, float* mean, float* rstd, void* ws,
                               size_t ws_bytes, const double* pre_part, int pre_npart, int B, int HW, int C, int flags, int dtype, void* stream) {
     int rc = gepi_check(B, HW, C, dtype, ws_bytes);
     if (rc) return rc;
     SGX_REQUIRE(x && noise && nw && mean && rstd, SGX_EINVAL, "gepi_stats: null argument");
     SGX_REQUIRE(!pre_part || pre_npart > 0, SGX_EINVAL, "gepi_stats: %d producer partials", pre_npart);
-    if (dtype == SGX_F32) return gepi_stats_t<float>(x, bias, noise, nw, mean, rstd, ws, pre_part, pre_npart, B, HW, C, flags, (hipStream_t)stream);
-    return gepi_stats_t<bf16_t>(x, bias, noise, nw, mean, rstd, ws, pre_part, pre_npart, B, HW, C, flags, (hipStream_t)stream);
+    return gepi_run(SGX_GEPI_PLAN_STATS, {x, nullptr, nullptr, bias, noise, nw, nullptr, mean, rstd, nullptr, nullptr, nullptr, pre_part, pre_npart, B, HW, C,
+                                          0, 0, (hipStream_t)stream}, flags, dtype, ws);
+}
+
+// Host-only: the plan the three entry points above would execute (include/sgx.h has the encoding)
+extern "C" int sgx_gepi_plan(int entry, int B, int HW, int C, int flags, int pre, int dtype, int* out) {
+    SGX_REQUIRE(entry >= SGX_GEPI_PLAN_FWD && entry <= SGX_GEPI_PLAN_STATS && out, SGX_EINVAL, "gepi_plan: bad args");
+    int rc = gepi_check(B, HW, C, dtype, (size_t)-1);
+    if (rc) return rc;
+    const GepiPlan p = gepi_plan(entry, B, HW, C, gepi_ve(dtype), flags, pre != 0);
+    const int v[SGX_GEPI_PLAN_INTS] = {p.small, p.pass, p.from_pre, p.fin, p.apply, p.nt, p.g.cvt, p.g.rows, p.g.rpt, p.g.chunk, p.g.nchunk,
+                                       p.nblk, p.pre_rows, p.fin2_B, p.fin2_n};
+    for (int i = 0; i < SGX_GEPI_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1146,35 +1243,25 @@ static BlurStatsGeom blur_stats_geom(int B, int H, int W, int C, int ve) {
     return g;
 }
 extern "C" int sgx_blur3x3_stats_nparts(int B, int H, int W, int C, int dtype) {
-    return blur_stats_geom(B, H, W, C, dtype == SGX_F32 ? 4 : 8).npart;
+    return blur_stats_geom(B, H, W, C, gepi_ve(dtype)).npart;
 }
 extern "C" int sgx_blur3x3_stats(const void* x, void* y, const float* bias, const float* noise, const float* nw, double* part,
                                  size_t part_bytes, int B, int H, int W, int C, int act, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "blur3x3_stats: bad dtype");
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE(C % ve == 0 && ((C / ve) <= 256 ? 256 % (C / ve) == 0 : (C / ve) % 256 == 0), SGX_EUNSUPPORTED, "blur3x3_stats: C=%d", C);
+    const int ve = gepi_ve(dtype);
+    SGX_REQUIRE(gepi_channels_ok(C, ve), SGX_EUNSUPPORTED, "blur3x3_stats: C=%d", C);
     SGX_REQUIRE(x && y && noise && nw && part, SGX_EINVAL, "blur3x3_stats: null argument");
     SGX_REQUIRE(act == SGX_ACT_NONE || act == SGX_ACT_LRELU, SGX_EINVAL, "blur3x3_stats: activation %d", act);
     const BlurStatsGeom g = blur_stats_geom(B, H, W, C, ve);
     SGX_REQUIRE(part_bytes >= (size_t)B * g.npart * C * 2 * sizeof(double), SGX_EWORKSPACE, "blur3x3_stats: partials buffer %zu < %zu",
                 part_bytes, (size_t)B * g.npart * C * 2 * sizeof(double));
     SGX_NOTE(0.0, 2.0 * (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * C, "blur_stats B%d %dx%d C%d", B, H, W, C);
-    const size_t shb = 256 * 2 * ve * sizeof(double);
-    if (dtype == SGX_F32)
-        hipLaunchKernelGGL(blur_stats_kernel<float>, dim3(g.npart, B), dim3(256), shb, st, (const float*)x, (float*)y, bias, noise, nw, part, H, W, C, g.cvt, g.wchunks, act, g.rt);
-    else
-        hipLaunchKernelGGL(blur_stats_kernel<bf16_t>, dim3(g.npart, B), dim3(256), shb, st, (const bf16_t*)x, (bf16_t*)y, bias, noise, nw, part, H, W, C, g.cvt, g.wchunks, act, g.rt);
-    SGX_LAUNCH_CHECK("blur_stats_kernel");
-    return 0;
-}
-
-extern "C" int sgx_gepi_bwd(const void* dy, const void* x, const float* bias, const float* noise, const float* nw,
-                            const float* style, const float* mean, const float* rstd, void* dx, float* dstyle, float* dnw,
-                            float* dbias, void* ws, size_t ws_bytes, int B, int HW, int C, int flags, int dtype, void* stream) {
-    int rc = gepi_check(B, HW, C, dtype, ws_bytes);
-    if (rc) return rc;
-    if (dtype == SGX_F32)
-        return gepi_bwd_t<float>(dy, x, bias, noise, nw, style, mean, rstd, dx, dstyle, dnw, dbias, ws, B, HW, C, flags, (hipStream_t)stream);
-    return gepi_bwd_t<bf16_t>(dy, x, bias, noise, nw, style, mean, rstd, dx, dstyle, dnw, dbias, ws, B, HW, C, flags, (hipStream_t)stream);
+    return gepi_by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(blur_stats_kernel<T>, dim3(g.npart, B), dim3(256), 256 * 2 * ve * sizeof(double), st, (const T*)x, (T*)y, bias, noise, nw, part, H, W, C,
+                           g.cvt, g.wchunks, act, g.rt);
+        SGX_LAUNCH_CHECK("blur_stats_kernel");
+        return 0;
+    });
 }

@@ -90,6 +90,7 @@ SIGNATURES = {
     "sgx_gepi_ws_bytes": (Z, [I, I, I]),
     "sgx_gepi_fwd": (I, [P, P, P, P, P, P, P, P, P, Z, P, I, I, I, I, I, I, P]),
     "sgx_gepi_stats": (I, [P, P, P, P, P, P, P, Z, P, I, I, I, I, I, I, P]),
+    "sgx_gepi_plan": (I, [I, I, I, I, I, I, I, P]),
     "sgx_rgb_out_epi": (I, [P, P, P, P, P, P, P, P, I, I, F, P, P, F, F, P, P, I, I, I, I, I, P]),
     "sgx_rgb_wgrad_epi_ws_bytes": (Z, [I, I, I]),
     "sgx_rgb_wgrad_epi": (I, [P, P, P, P, P, P, P, P, P, P, I, I, F, F, P, Z, I, I, I, I, P]),

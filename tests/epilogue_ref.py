@@ -174,7 +174,7 @@ def kink_cap(n):
 # ---------------------------------------------------------------------------------------------------------------- launcher rules
 # csrc/gepi.hip restated: which kernels a call launches, and the fp32 chain lengths that follow from the geometry.
 Geom = namedtuple("Geom", "cvt rows rpt chunk nchunk")
-ENV_DEFAULT = dict(apply1=1, bwd2s=1, fold=1, nt_mb=192.0)
+ENV_DEFAULT = dict(apply1=1, bwd2s=1, fold=1, nt_mb=192.0, small=1, rpt=64)
 GROUPS = {                                                   # the process-wide switches of a group: read once per process
     "default": {},
     "switch": {"SGX_GEPI_APPLY1": "2", "SGX_GEPI_BWD2S": "2"},
@@ -186,15 +186,16 @@ GROUPS = {                                                   # the process-wide 
 def group_env(group):
     e, g = dict(ENV_DEFAULT), GROUPS[group]
     e.update(apply1=int(g.get("SGX_GEPI_APPLY1", 1)), bwd2s=int(g.get("SGX_GEPI_BWD2S", 1)), fold=int(g.get("SGX_GEPI_FOLD", 1)),
-             nt_mb=float(g.get("SGX_NT_MIN_MB", 192.0)))
+             nt_mb=float(g.get("SGX_NT_MIN_MB", 192.0)), small=int(g.get("SGX_GEPI_SMALL", 1)), rpt=int(g.get("SGX_GEPI_RPT", 64)))
     return e
 
 
-def gepi_geom(B, HW, C, ve):
+def gepi_geom(B, HW, C, ve, rpt=64):
+    """rpt: SGX_GEPI_RPT, the most pixel rows per thread (<= 0: 64)."""
     cv = C // ve
     cvt = min(cv, 256)
     rows = 256 // cvt
-    rpt = 64
+    rpt = rpt if rpt > 0 else 64
     while rpt > 8 and B * ((HW + rows * rpt - 1) // (rows * rpt)) < 512:
         rpt >>= 1
     return Geom(cvt, rows, rpt, rows * rpt, (HW + rows * rpt - 1) // (rows * rpt))
@@ -206,10 +207,10 @@ def gs_plan(dt, HW):
     return 4 * (512 // nv), (0 if HW <= 2 * (256 // nv) else 1)
 
 
-def gepi_small_ok(B, HW, C, dt):
+def gepi_small_ok(B, HW, C, dt, small=1):
     mx, _ = gs_plan(dt, HW)
     nbytes = B * HW * C * (4 if dt == F else 2)
-    return C % 16 == 0 and B * (C // 16) >= 64 and (HW <= mx // 4 or (HW <= mx and nbytes <= (8 << 20)))
+    return small != 0 and C % 16 == 0 and B * (C // 16) >= 64 and (HW <= mx // 4 or (HW <= mx and nbytes <= (8 << 20)))
 
 
 def _small(kind, dt, HW):
@@ -222,7 +223,7 @@ def fwd_kernels(B, HW, C, dt, flags, pre, env):
     tail = ["gepi_fin_stats", f"gepi_apply1<{t}>"] if apply1 else None
     if norm and pre:
         return tail or ["gepi_fin_stats", f"gepi_apply<{t}>"]
-    if gepi_small_ok(B, HW, C, dt):
+    if gepi_small_ok(B, HW, C, dt, env["small"]):
         return [_small("fwd", dt, HW)]
     k = [f"gepi_pass<{t}, 0, false>"] if norm else []
     if tail:
@@ -230,22 +231,22 @@ def fwd_kernels(B, HW, C, dt, flags, pre, env):
     return k + ([f"gepi_apply<{t}>"] if env["fold"] else ["gepi_fin_stats", f"gepi_apply<{t}>"])
 
 
-def bwd2s_route(B, HW, C, dt):
+def bwd2s_route(B, HW, C, dt, rpt=64):
     """(blocks per image, rows left for gepi_fin_bwd2 after the pre-reduction or 0 when it reads the block partials itself)."""
     ve = _ve(dt)
     nblk = (HW * (C // ve) + 1023) // 1024
     K = B * nblk
     NB = min(K, 256)
-    return nblk, (NB if NB <= B * gepi_geom(B, HW, C, ve).nchunk and 2 * C <= 256 else 0)
+    return nblk, (NB if NB <= B * gepi_geom(B, HW, C, ve, rpt).nchunk and 2 * C <= 256 else 0)
 
 
 def bwd_kernels(B, HW, C, dt, env):
     t, ve, nb = tname(dt), _ve(dt), (4 if dt == F else 2) * B * HW * C
-    if gepi_small_ok(B, HW, C, dt):
+    if gepi_small_ok(B, HW, C, dt, env["small"]):
         return [_small("bwd", dt, HW), "gepi_fin_bwd2"]
     k, cv = [f"gepi_pass<{t}, 1, false>"], C // ve
     if env["bwd2s"] != 0 and C <= 128 and cv in (1, 2, 4, 8, 16) and (env["bwd2s"] == 2 or nb >= 800e6):
-        return k + ["gepi_fin_bwd1", f"gepi_bwd2s<{t}>"] + (["gepi_rows_prereduce"] if bwd2s_route(B, HW, C, dt)[1] else []) + ["gepi_fin_bwd2"]
+        return k + ["gepi_fin_bwd1", f"gepi_bwd2s<{t}>"] + (["gepi_rows_prereduce"] if bwd2s_route(B, HW, C, dt, env["rpt"])[1] else []) + ["gepi_fin_bwd2"]
     if env["fold"]:
         return k + [f"gepi_pass<{t}, 2, {'true' if nb >= env['nt_mb'] * 1e6 else 'false'}>", "gepi_fin_bwd2"]
     return k + ["gepi_fin_bwd1", f"gepi_pass<{t}, 2, false>", "gepi_fin_bwd2"]
@@ -439,7 +440,8 @@ REJECTIONS = [
 # Launch sites of csrc/gepi.hip / csrc/optim.hip that no row reaches, with the reason (tests/test_epilogue_coverage.py)
 EXCLUDED_SITES = {}
 EXCLUDED_PATHS = {
-    "SGX_GEPI_SMALL=0 / SGX_GEPI_RPT / SGX_GEPI_APPLY1=0 / SGX_GEPI_BWD2S=0": "A/B switches read once per process; their kernels are the two-pass rows'",
+    "SGX_GEPI_SMALL=0 / SGX_GEPI_RPT / SGX_GEPI_APPLY1=0 / SGX_GEPI_BWD2S=0": "A/B switches read once per process; their kernels are the two-pass rows', "
+                                                                             "and what they select is planned on the CPU by tests/test_gepi_plan.py",
 }
 # Launch paths (group, kernel list with the dtype written T) that have no integer row, each with the reason; every other path must have one
 NO_INTEGER_ROW = {

@@ -4,6 +4,7 @@ epilogue_ref, select for every row's own arguments exactly the kernels the row n
 the kernels' lane chains and fails planted errors of the kinds this family is prone to, which the suite's rel-L2 metric lets through."""
 import collections
 import os
+import re
 
 import pytest
 import torch
@@ -28,7 +29,8 @@ def sites():
 
 def test_every_launch_site_is_claimed_or_excused():
     ge, op = sites()
-    assert len(ge) >= 30 and len(op) == 4, (len(ge), len(op))        # the scan found the launchers
+    assert len(ge) == 16 and len(op) == 4, (len(ge), len(op))        # the scan found the launchers: one site per kernel instantiation (dtype aside)
+    assert len({s[0] + s[1] for s in ge}) == 16
     assert unclaimed(ge, ER.CASES, ER.EXCLUDED_SITES) == []
     assert unclaimed(op, OPTIM_ROWS, ER.EXCLUDED_SITES) == []
     assert any(k.startswith("blur_stats_kernel") for c in ER.CASES if c.entry == "sgx_blur3x3_stats" for k in c.kernels)
@@ -39,6 +41,13 @@ def test_every_launch_site_is_claimed_or_excused():
             assert any(claims(s, k) for s in ge), (c.id, k)
         assert c.why and c.group in ER.GROUPS and (c.entry, c.group) in ROWS, c.id
     assert len(ER.GROUPS) - 1 <= 3                                   # at most three child processes
+    # every switch the launchers read is an SGX_SWITCH accessor, set by a group or excused by name (and planned by tests/test_gepi_plan.py)
+    with open(os.path.join(CSRC, "gepi.hip")) as f:
+        src = f.read()
+    read = set(re.findall(r'SGX_SWITCH\(\s*\w+\s*,\s*"(SGX_[A-Z0-9_]*)"', src))
+    assert read == {"SGX_GEPI_RPT", "SGX_GEPI_SMALL", "SGX_GEPI_APPLY1", "SGX_GEPI_BWD2S", "SGX_GEPI_FOLD"} and "getenv" not in src
+    excused = " ".join(ER.EXCLUDED_PATHS)
+    assert all(any(k in g for g in ER.GROUPS.values()) or k in excused for k in read), read
 
 
 def test_a_new_kernel_or_a_dropped_row_is_noticed():
@@ -51,7 +60,7 @@ def test_a_new_kernel_or_a_dropped_row_is_noticed():
     no_nt = [c for c in ER.CASES if c.group != "switch_nt"]
     assert unclaimed(ge, no_nt, ER.EXCLUDED_SITES) == ["gepi_pass<T, 2, true>"]
     no_f32_apply1 = [c for c in ER.CASES if "gepi_apply1<float>" not in c.kernels]
-    assert unclaimed(ge, no_f32_apply1, ER.EXCLUDED_SITES) == ["gepi_apply1<T> for ['float']"] * 2
+    assert unclaimed(ge, no_f32_apply1, ER.EXCLUDED_SITES) == ["gepi_apply1<T> for ['float']"] * 1
     assert unclaimed(op, OPTIM_ROWS[1:], ER.EXCLUDED_SITES) == ["sumsq_stage1", "sumsq_stage2"]
     assert dict(collections.Counter((c.entry, c.group) for c in ER.CASES)) == ROWS
 
