@@ -242,6 +242,28 @@ int sgx_rgb_out(const void* x, const float* w, int sj, int sc, float wscale, con
 int sgx_rgb_in_add(const float* img, const float* w, int sj, int sc, float wscale, const void* add, void* y, size_t npix, int C, int dtype,
                    void* stream);
 size_t sgx_rgb_wgrad_ws_bytes(size_t npix, int C);
+/* The same 1x1 layers for images that are not RGB (csrc/imgconv.hip): J image channels, images fp32 [p][J], the weight read in place
+ * with element (j, c) at w[j*sj + c*sc] * wscale (from_rgb [C][J][1][1]: sj=1, sc=J; to_rgb [J][C][1][1]: sj=C, sc=1).  J = 1, 2, 4
+ * (num_channels of a grayscale / two-channel / RGBA model) and 8 (the conditional discriminator's from_rgb over [RGBA image, label
+ * embedding], models/GAN.py:326-330, and its adjoint).  C % 4 == 0 (fp32) / C % 8 == 0 (bf16), anything else is
+ * SGX_EUNSUPPORTED before any launch; img aligned to 4 J bytes (16 for J = 8), activations to 16.
+ *   sgx_img_in : y[p][c] = bias[c] + wscale * sum_j img[p][j]*W(j,c)     from_rgb forward, to_rgb data gradient:
+ *                                                                        models/GAN.py:358-359,377-378 (adjoint of :157,167)
+ *   sgx_img_out: img[p][j] = bias[j] + wscale * sum_c x[p][c]*W(j,c)     to_rgb forward, from_rgb data gradient, the R1 inner gradient:
+ *                                                                        models/GAN.py:157,167 (adjoint of :358-359,377-378)
+ *   sgx_img_wgrad: dw[j*sj + c*sc] = wscale * sum_p img[p][j]*f[p][c]    both layers' weight gradient, in the parameter layout; fp64
+ *                  partials per block finished in a fixed order (no atomics): the same bits at every run.  ws: sgx_img_wgrad_ws_bytes. */
+int sgx_img_in(const float* img, const float* w, int J, int sj, int sc, float wscale, const float* bias, void* y, size_t npix, int C, int dtype,
+               void* stream);
+int sgx_img_out(const void* x, const float* w, int J, int sj, int sc, float wscale, const float* bias, float* img, size_t npix, int C, int dtype,
+                void* stream);
+size_t sgx_img_wgrad_ws_bytes(size_t npix, int J, int C);
+int sgx_img_wgrad(const float* img, const void* f, float* dw, int J, int sj, int sc, float wscale, void* ws, size_t ws_bytes, size_t npix, int C,
+                  int dtype, void* stream);
+/* sgx_images_u8_to_nhwc for J = 1..4 channels (data/transforms.py:20-33 on grayscale / RGBA data): src [B][H][W][J] bytes, or [B][J][H][W]
+ * if src_chw; the same arithmetic in the same order, so J = 3 gives the bits of the 3-channel entry point.  Any W (a multiple of 4 takes
+ * the vector kernel). */
+int sgx_images_u8_to_nhwc_c(const void* src, void* dst, const int* flip, int B, int H, int W, int J, int src_chw, int dtype, void* stream);
 /* real images at the current depth with the fade-in blend (models/GAN.py:575-586): out = alpha * x + beta *
  * nearest_up2(avgpool2(x)) on fp32 [B][H][W][3] in one pass; ab_dev as in sgx_rgb_out_fade. */
 int sgx_downsample_fade_rgb(const float* x, float* out, int B, int H, int W, float alpha, float beta, const float* ab_dev, void* stream);

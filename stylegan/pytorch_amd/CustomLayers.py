@@ -239,8 +239,17 @@ class EqualizedConv2d(nn.Module):
                     y = part if y is None else F.call(F.AxpbyFn, y, part, 1.0, 1.0)
             elif cout == 3:
                 y = F.call(F.RgbOutFn, x, self.weight, bias, self.w_mul)
+            elif cin in F.IMG_CHANNELS and x.shape[3] == cin and cout not in F.IMG_CHANNELS:
+                # from_rgb of a model that is not RGB (num_channels 1, 2, 4), and of its conditional discriminator ([image, label
+                # embedding]: 2 * num_channels input channels, reference models/GAN.py:326-330) in ONE call (csrc/imgconv.hip)
+                s = float(out_scale)
+                y = F.call(F.ImgInFn, x.float(), self.weight, bias if s == 1.0 or bias is None else bias * s, self.w_mul * s,
+                           out_dtype or torch.float32)
+            elif cout in (1, 2, 4):
+                y = F.call(F.ImgOutFn, x, self.weight, bias, self.w_mul, cout)        # to_rgb of such a model
             else:
-                raise NotImplementedError("1x1 EqualizedConv2d is built for the to_rgb / from_rgb layers (3 channels on one side)")
+                raise NotImplementedError("1x1 EqualizedConv2d is built for the to_rgb / from_rgb layers (1, 2, 3 or 4 image channels on one "
+                                          "side; twice that on the input side of a conditional discriminator)")
             return F.call(F.BiasActFn, y, None, 1.0, act) if act else y
         assert self.kernel_size == 3
         if epi_stats is not None:
@@ -302,7 +311,7 @@ class EqualizedConv2d(nn.Module):
         return F.call(F.BiasActFn, y, bias, 1.0, act) if (bias is not None or act) else y
 
     def forward(self, x):
-        if self.kernel_size == 1 and self.weight.shape[0] == 3:
+        if self.kernel_size == 1 and self.weight.shape[0] in (1, 2, 3, 4):
             return F.nchw_view(self.forward_nhwc(F.nhwc(x)))
         xin = F.nhwc(x, torch.float32)
         return F.nchw_view(self.forward_nhwc(xin))

@@ -359,6 +359,9 @@ class Discriminator(nn.Module):
         # 'color,xflip,rot90,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
+        if self._diffaug_bits and num_channels != 3:
+            raise ValueError(f"diffaug_policy {self.diffaug_policy!r} needs num_channels == 3, got {num_channels}: the DiffAugment / ADA "
+                             "kernels are 3-channel by construction (the colour ops mix R, G and B)")
         # ADA (Karras et al., NeurIPS 2020) on top of the policy: each op with probability p, p steered on the device towards
         # E[sign(D(real))] == ada_target (0: off -- no buffer, the policy applies always, exactly the code path without these keys)
         self.ada_target, self.ada_interval = float(ada_target), int(ada_interval)

@@ -1793,6 +1793,115 @@ class RgbWgradFn(Function):
 
 
 # ---------------------------------------------------------------------------------------------------
+# The same 1x1 layers for images that are not RGB (csrc/imgconv.hip): J = num_channels in {1, 2, 4} image channels, and J = 2 * num_channels
+# in {2, 4, 8} on the input side of the conditional discriminator's from_rgb.  Images are fp32 [B,H,W,J]; the weight is the raw
+# parameter ([C,J,1,1] from_rgb or [J,C,1,1] to_rgb), read in place.  ImgInFn -> ImgOutFn / ImgWgradFn -> ImgInFn ...: the chain closes
+# under differentiation, so the R1 penalty's double backward runs through from_rgb exactly as it does through the Rgb functions.
+IMG_CHANNELS = (1, 2, 4, 8)
+
+
+def img_layout(weight, J):
+    """(sj, sc, C) of a 1x1 parameter with ``J`` channels on its image side: from_rgb [C,J,1,1] or to_rgb [J,C,1,1].  A [J,J,1,1]
+    parameter is ambiguous and refused."""
+    J = int(J)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or J not in IMG_CHANNELS:
+        raise N.SgxError(f"img_layout: need a 1x1 parameter and J in {IMG_CHANNELS}, got {tuple(weight.shape)}, J={J}")
+    if weight.shape[1] == J and weight.shape[0] != J:
+        return 1, J, weight.shape[0]
+    if weight.shape[0] == J and weight.shape[1] != J:
+        return weight.shape[1], 1, weight.shape[1]
+    raise N.SgxError(f"1x1 convolution with {J} image channels: the parameter {tuple(weight.shape)} must have them on exactly one side")
+
+
+class ImgInFn(Function):
+    """f[p][c] = bias[c] + wscale * sum_j img[p][j] * W(j,c), J = img.shape[3] in {1, 2, 4, 8}."""
+
+    @staticmethod
+    def forward(ctx, img, weight, bias, wscale, out_dtype):
+        img, w = _c(img), _c(weight.detach())
+        B, H, W, J = img.shape
+        sj, sc, C = img_layout(w, J)
+        if img.dtype != torch.float32:
+            raise N.SgxError("ImgInFn: the image must be fp32 NHWC")
+        y = torch.empty((B, H, W, C), dtype=out_dtype, device=img.device)
+        N.check(N.lib().sgx_img_in(N.ptr(img), N.ptr(w), J, sj, sc, float(wscale), N.ptr(None if bias is None else _c(bias.detach())), N.ptr(y),
+                                   B * H * W, C, _dtype_code(out_dtype), N.stream()), "sgx_img_in")
+        ctx.has_bias, ctx.wscale = bias is not None, float(wscale)
+        ctx.save_for_backward(img, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        img, weight = ctx.saved_tensors
+        g = _c(g)
+        gi = gw = gb = None
+        if _want_image_grad(ctx, 0):
+            gi = _bcall(ImgOutFn, g, weight, None, ctx.wscale, img.shape[3])
+        if not _DATA_GRAD_ONLY:
+            if ctx.needs_input_grad[1]:
+                gw = _bcall(ImgWgradFn, img, g, weight, ctx.wscale)
+            if ctx.has_bias and ctx.needs_input_grad[2]:
+                gb = _bcall(ColSumFn, g, 1.0)
+        return gi, gw, gb, None, None
+
+
+class ImgOutFn(Function):
+    """img[p][j] = bias[j] + wscale * sum_c x[p][c] * W(j,c), j < J in {1, 2, 4} (to_rgb) or 8 (the adjoint of a conditional from_rgb)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, wscale, J):
+        x, w = _c(x), _c(weight.detach())
+        J = int(J)
+        sj, sc, C = img_layout(w, J)
+        B, H, W, Cx = x.shape
+        if Cx != C:
+            raise N.SgxError(f"ImgOutFn: x has {Cx} channels, the parameter {C}")
+        img = torch.empty((B, H, W, J), dtype=torch.float32, device=x.device)
+        N.check(N.lib().sgx_img_out(N.ptr(x), N.ptr(w), J, sj, sc, float(wscale), N.ptr(None if bias is None else _c(bias.detach())), N.ptr(img),
+                                    B * H * W, C, N.dt(x), N.stream()), "sgx_img_out")
+        ctx.has_bias, ctx.wscale = bias is not None, float(wscale)
+        ctx.save_for_backward(x, weight)
+        return img
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        g = _c(g)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = _bcall(ImgInFn, g, weight, None, ctx.wscale, x.dtype)
+        if not _DATA_GRAD_ONLY:
+            if ctx.needs_input_grad[1]:
+                gw = _bcall(ImgWgradFn, g, x, weight, ctx.wscale)
+            if ctx.has_bias and ctx.needs_input_grad[2]:
+                gb = _bcall(ColSumFn, g, 1.0)                   # J numbers
+        return gx, gw, gb, None, None
+
+
+class ImgWgradFn(Function):
+    """dW(j,c) = wscale * sum_p img[p][j] * f[p][c], written in the parameter's layout; fixed-order sums (run-to-run identical bits).
+    First order."""
+
+    @staticmethod
+    def forward(ctx, img, f, weight, wscale):
+        img, f = _c(img), _c(f)
+        J = img.shape[-1]
+        sj, sc, C = img_layout(weight, J)
+        npix = img.numel() // J
+        dw = torch.empty_like(weight, dtype=torch.float32, memory_format=torch.contiguous_format)
+        L = N.lib()
+        ws = N.workspace(L.sgx_img_wgrad_ws_bytes(npix, J, C), f.device)
+        N.check(L.sgx_img_wgrad(N.ptr(img), N.ptr(f), N.ptr(dw), J, sj, sc, float(wscale), N.ptr(ws), ws.numel(), npix, C, N.dt(f),
+                                N.stream()), "sgx_img_wgrad")
+        return dw
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        raise NotImplementedError("second derivative through a weight gradient is not part of the training path")
+
+
+# ---------------------------------------------------------------------------------------------------
 class GEpilogueFn(Function):
     """noise + LeakyReLU + InstanceNorm + StyleMod (reference LayerEpilogue), conv bias folded in.  First order.
     ``flags``: EPI_ACT | EPI_NORM select the activation / instance-norm stages (default both); ``noise``/``nw`` None = no
@@ -2279,9 +2388,13 @@ def images_from_uint8(u8, flip=None, out_dtype=torch.float32, layout=None):
     """uint8 image batch on the GPU -> the ``real_batch`` the training step takes: logical [B,3,H,W] view over NHWC storage,
     (v/255 - 0.5)/0.5 -- the reference's ToTensor + Normalize (data/transforms.py:27-32) done on the device, so the batch
     crosses PCIe as bytes.  ``u8``: [B,H,W,3] (decoded images; ``layout='hwc'``) or [B,3,H,W] (``'chw'``; inferred when
-    unambiguous).  ``flip``: per-image horizontal-flip decisions (RandomHorizontalFlip, drawn by the caller), or None."""
+    unambiguous).  ``flip``: per-image horizontal-flip decisions (RandomHorizontalFlip, drawn by the caller), or None.
+    Images with 1, 2 or 4 channels (grayscale, gray + alpha, RGBA): [B,H,W,J] / [B,J,H,W] with ``layout`` given explicitly (the
+    inference is for 3 channels only) -> logical [B,J,H,W], through ``sgx_images_u8_to_nhwc_c``."""
     if not (u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4):
         raise N.SgxError("images_from_uint8: need a 4-d uint8 GPU tensor")
+    if layout is not None and layout not in ("hwc", "chw"):
+        raise N.SgxError(f"images_from_uint8: layout must be 'hwc' or 'chw', got {layout!r}")
     if layout is None:
         hwc, chw = u8.shape[3] == 3, u8.shape[1] == 3
         if hwc == chw:
@@ -2289,14 +2402,21 @@ def images_from_uint8(u8, flip=None, out_dtype=torch.float32, layout=None):
         layout = "hwc" if hwc else "chw"
     u8 = _c(u8)
     B, H, W = (u8.shape[0], u8.shape[1], u8.shape[2]) if layout == "hwc" else (u8.shape[0], u8.shape[2], u8.shape[3])
+    J = int(u8.shape[3] if layout == "hwc" else u8.shape[1])
+    if J not in (1, 2, 3, 4):
+        raise N.SgxError(f"images_from_uint8: {J} channels in layout {layout!r} of {tuple(u8.shape)} (1 to 4 channels)")
     fl = None
     if flip is not None:
         fl = torch.as_tensor(flip).to(device=u8.device, dtype=torch.int32).contiguous()
         if fl.numel() != B:
             raise N.SgxError("images_from_uint8: one flip decision per image")
-    out = torch.empty((B, H, W, 3), dtype=out_dtype, device=u8.device)
-    N.check(N.lib().sgx_images_u8_to_nhwc(N.ptr(u8), N.ptr(out), N.ptr(fl), B, H, W, int(layout == "chw"), N.dt(out), N.stream()),
-            "sgx_images_u8_to_nhwc")
+    out = torch.empty((B, H, W, J), dtype=out_dtype, device=u8.device)
+    if J == 3:
+        N.check(N.lib().sgx_images_u8_to_nhwc(N.ptr(u8), N.ptr(out), N.ptr(fl), B, H, W, int(layout == "chw"), N.dt(out), N.stream()),
+                "sgx_images_u8_to_nhwc")
+    else:
+        N.check(N.lib().sgx_images_u8_to_nhwc_c(N.ptr(u8), N.ptr(out), N.ptr(fl), B, H, W, J, int(layout == "chw"), N.dt(out), N.stream()),
+                "sgx_images_u8_to_nhwc_c")
     return nchw_view(out)
 
 

@@ -76,6 +76,11 @@ SIGNATURES = {
     "sgx_rgb_in": (I, [P, P, I, I, F, P, P, Z, I, I, P]),
     "sgx_rgb_in_add": (I, [P, P, I, I, F, P, P, Z, I, I, P]),
     "sgx_rgb_out": (I, [P, P, I, I, F, P, P, Z, I, I, P]),
+    "sgx_img_in": (I, [P, P, I, I, I, F, P, P, Z, I, I, P]),
+    "sgx_img_out": (I, [P, P, I, I, I, F, P, P, Z, I, I, P]),
+    "sgx_img_wgrad_ws_bytes": (Z, [Z, I, I]),
+    "sgx_img_wgrad": (I, [P, P, P, I, I, I, F, P, Z, Z, I, I, P]),
+    "sgx_images_u8_to_nhwc_c": (I, [P, P, P, I, I, I, I, I, I, P]),
     "sgx_downsample_fade_rgb": (I, [P, P, I, I, I, F, F, P, P]),
     "sgx_diffaug_ws_bytes": (Z, [I, I, I]),
     "sgx_diffaug": (I, [P, P, P, I, I, I, I, I, I, P, Z, P]),
