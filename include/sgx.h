@@ -45,10 +45,13 @@ int sgx_selftest_tr16(void* out256, void* stream);
  * stream itself.  sgx_prof_start(1, 0): record every launch (clears earlier records); (2, i): record only launches of
  * the kernel that record i belongs to; (0, 0): stop, keeping the records.  sgx_prof_get waits for record i and returns
  * the demangled kernel name (as rocprofv3 prints it), the milliseconds between its events, and the flops, algorithmic
- * bytes and layer description attached by the entry point that launched it (0 / "" when it attached none). */
+ * bytes and layer description attached by the entry point that launched it (0 / "" when it attached none).
+ * sgx_prof_get_launch returns record i's launch geometry as the runtime was given it: grid3 and block3 take x, y, z,
+ * lds the dynamic LDS bytes (any of the three may be NULL); it waits for nothing. */
 int sgx_prof_start(int mode, int only_of);
 int sgx_prof_count(void);
 int sgx_prof_get(int i, char* name, int name_cap, float* ms, double* flops, double* bytes, char* desc, int desc_cap);
+int sgx_prof_get_launch(int i, unsigned* grid3, unsigned* block3, size_t* lds);
 
 /* ---------------------------------------------------------------- convolutions (MFMA implicit GEMM)
  * Packed weight layout for all three: w[tap][n][k], n = output channel of THIS launch, k = reduction

@@ -38,7 +38,7 @@ extern "C" int sgx_selftest_tr16(void* out256, void* stream) {
 int sgx_prof_mode = 0;
 const void* sgx_prof_only_fn = nullptr;
 namespace {
-struct ProfRec { const void* fn; hipEvent_t e0, e1; double flops, bytes; char desc[56]; };
+struct ProfRec { const void* fn; hipEvent_t e0, e1; double flops, bytes; char desc[56]; unsigned grid[3], block[3]; size_t lds; };
 struct ProfNote { bool set; double flops, bytes; char desc[56]; };
 std::mutex g_prof_mu;                                      // launches come from the caller's and autograd's threads
 std::vector<ProfRec> g_recs;
@@ -59,13 +59,16 @@ void sgx_prof_note(double flops, double bytes, const char* fmt, ...) {
     vsnprintf(g_note.desc, sizeof(g_note.desc), fmt, ap);
     va_end(ap);
 }
-void sgx_prof_begin(const void* fn, hipStream_t st, int* slot) {
+void sgx_prof_begin(const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t st, int* slot) {
     ProfNote note = g_note;
     g_note.set = false;                                    // a note describes exactly one launch
     if (sgx_prof_mode == 2 && fn != sgx_prof_only_fn) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     ProfRec r;
     r.fn = fn; r.e0 = prof_event(); r.e1 = prof_event();
+    r.grid[0] = grid.x; r.grid[1] = grid.y; r.grid[2] = grid.z;
+    r.block[0] = block.x; r.block[1] = block.y; r.block[2] = block.z;
+    r.lds = lds;
     r.flops = note.set ? note.flops : 0.0; r.bytes = note.set ? note.bytes : 0.0;
     snprintf(r.desc, sizeof(r.desc), "%s", note.set ? note.desc : "");
     if (!r.e0 || !r.e1) return;
@@ -124,6 +127,18 @@ extern "C" int sgx_prof_get(int i, char* name, int name_cap, float* ms, double* 
         if (e == hipSuccess) e = hipEventElapsedTime(ms, r.e0, r.e1);
         SGX_REQUIRE(e == hipSuccess, (int)e, "prof_get: %s", hipGetErrorString(e));
     }
+    return 0;
+}
+// Record i: the launch geometry as it was given to the runtime (grid and block in x, y, z; dynamic LDS bytes).  Waits for nothing.
+extern "C" int sgx_prof_get_launch(int i, unsigned* grid3, unsigned* block3, size_t* lds) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    SGX_REQUIRE(i >= 0 && i < (int)g_recs.size(), SGX_EINVAL, "prof_get_launch: record %d of %d", i, (int)g_recs.size());
+    const ProfRec& r = g_recs[i];
+    for (int k = 0; k < 3; ++k) {
+        if (grid3) grid3[k] = r.grid[k];
+        if (block3) block3[k] = r.block[k];
+    }
+    if (lds) *lds = r.lds;
     return 0;
 }
 

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "sgx.h"
 
 typedef unsigned short bf16_t;                                       // raw bf16 storage
@@ -86,19 +87,23 @@ __device__ __forceinline__ void st16(void* p, const uint4& q, bool nt) {
     if (nt) { const sgx_v4u v = {q.x, q.y, q.z, q.w}; __builtin_nontemporal_store(v, reinterpret_cast<sgx_v4u*>(p)); }
     else *reinterpret_cast<uint4*>(p) = q;
 }
-// launches use the hint for tensors of at least this many bytes (SGX_NT_MIN_MB; 0 = never): smaller ones are the next kernel's cache hits
-static inline bool sgx_nt_for(double tensor_bytes) {
-    static const double min_bytes = [] { const char* e = getenv("SGX_NT_MIN_MB"); const double mb = e ? atof(e) : 192.0; return mb > 0 ? mb * 1e6 : 1e300; }();
-    return tensor_bytes >= min_bytes;
-}
-// An integer switch of the environment.  SGX_SWITCH names the accessor of one switch: the value is read at its first
-// call and kept for the process, every use site calls the accessor
+// A switch of the environment.  SGX_SWITCH names the accessor of one integer switch, SGX_SWITCH_F of one that takes
+// fractions: the value is read at the accessor's first call and kept for the process, every use site calls the accessor
 static inline int sgx_env_int(const char* name, int def) {
     const char* e = getenv(name);
     return e ? atoi(e) : def;
 }
+static inline double sgx_env_float(const char* name, double def) {
+    const char* e = getenv(name);
+    return e ? atof(e) : def;
+}
 #define SGX_SWITCH(fn, name, def) \
-    static int fn() { static const int v = sgx_env_int(name, def); return v; }
+    static inline int fn() { static const int v = sgx_env_int(name, def); return v; }
+#define SGX_SWITCH_F(fn, name, def) \
+    static inline double fn() { static const double v = sgx_env_float(name, def); return v; }
+// launches use the hint for tensors of at least this many MB (0 or less = never): smaller ones are the next kernel's cache hits
+SGX_SWITCH_F(sgx_nt_min_mb, "SGX_NT_MIN_MB", 192.0)
+static inline bool sgx_nt_for(double tensor_bytes) { return sgx_nt_min_mb() > 0 && tensor_bytes >= sgx_nt_min_mb() * 1e6; }
 // XCD-band tile order of the persistent convolution grids, both kernel generations.  Measured (round 2): halo
 // over-fetch gone (PMC), 80.8 vs 81.2 ms at batch 32, nothing at batch 4
 inline int sgx_tile_bands_on() { static const int v = sgx_env_int("SGX_TILE_BANDS", 1); return v; }
@@ -138,7 +143,51 @@ void sgx_set_error(const char* fmt, ...);
     } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool sgx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int sgx_ncu();                                             // compute units of the current device (api.hip)
+
+// ---- grids of the streaming kernels (pointwise.hip, imgconv.hip): 256-thread blocks, one 16-byte vector per lane per trip -----------
+SGX_SWITCH(sgx_grid_cap, "SGX_GRID_CAP", 8192)             // blocks of a grid_for launch; 0 or less = no cap
+SGX_SWITCH(sgx_grid_all_cap, "SGX_GRID_ALL_CAP", 0)        // A/B: blocks of a grid_all launch; 0 or less (the default) = no cap
+static inline unsigned sgx_grid_capped(size_t nvec, int cap) {
+    size_t g = (nvec + 255) / 256;
+    const size_t most = cap > 0 ? (size_t)cap : (size_t)0x7fffffffL;
+    if (g > most) g = most;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+// The grid of a grid-stride loop whose threads amortise a setup over their trips (hoisted weights, a block's LDS table): at most
+// SGX_GRID_CAP blocks.
+static inline unsigned grid_for(size_t nvec) { return sgx_grid_capped(nvec, sgx_grid_cap()); }
+// The grid of a pass whose threads have NO per-thread setup worth amortising (pure elementwise kernels, the blur's strips): one trip of the
+// kernel's grid-stride loop per thread.  Round 6, tools/stream_probe.hip + the step's layer tables with SGX_GRID_CAP=0: a read + write stream
+// runs at 6.1-6.2 TB/s as short-lived blocks against 5.0-5.1 under the 8192-block cap above (lrelu_bwd_bits 214 -> 184 us, lrelu_bwd 148 ->
+// 126, up2+add 164 -> 146, the blurs -2..4 %); kernels that hoist weights per thread (rgb_in / rgb_out / fade_rgb_bwd2) lose and keep the cap.
+static inline unsigned grid_all(size_t nvec) { return sgx_grid_capped(nvec, sgx_grid_all_cap()); }
+// grid_for for a loop kernel that hoists its channel group's weights (rgb_in_kernel, img_in_kernel): the grid stride (256 * blocks) must be
+// a multiple of the cv vectors of a pixel
+static inline unsigned grid_for_hoisted(size_t nvec, int cv) {
+    unsigned g = grid_for(nvec);
+    if (256 % cv != 0) g = (g + cv - 1) / cv * cv;
+    return g;
+}
+
+// ---- activation dtype -> element type, once (the streaming entry points) ----------------------------------------------------------------
+// sgx_by_dtype(dtype, who, f) calls f(T{}) with T = float for SGX_F32 and bf16_t for SGX_BF16 and returns what it returns; any other value
+// is SGX_EINVAL, and f is not called.  In f: using T = decltype(t); the casts of the void* arguments are as<T>(p).
+template <typename T> static inline const T* as(const void* p) { return static_cast<const T*>(p); }
+template <typename T> static inline T* as(void* p) { return static_cast<T*>(p); }
+static inline bool sgx_dtype_ok(int dtype) { return dtype == SGX_F32 || dtype == SGX_BF16; }
+static inline double sgx_esize(int dtype) { return dtype == SGX_F32 ? 4.0 : 2.0; }       // bytes per element, for the SGX_NOTE lines
+template <typename F> static inline int sgx_by_dtype(int dtype, const char* who, F f) {
+    SGX_REQUIRE(sgx_dtype_ok(dtype), SGX_EINVAL, "%s: dtype %d (SGX_F32 or SGX_BF16)", who, dtype);
+    return dtype == SGX_F32 ? f(float{}) : f(bf16_t{});
+}
+// The same for a small set of compile-time integers: f(std::integral_constant<int, J>{}) for the J of the list that equals j -> true; false
+// (and no call) when none does.
+template <int... Js, typename F> static inline bool sgx_by_int(int j, F f) {
+    return ((j == Js ? (f(std::integral_constant<int, Js>{}), true) : false) || ...);
+}
 
 // ---- between the convolution files (geo: 0 = 3x3, 1 = 4x4 stride 2, 2 = 4x4 stride 2 transposed) ---------------------------------
 static inline int sgx_conv_out(int geo, int n) { return geo == 1 ? n / 2 : (geo == 2 ? 2 * n : n); }      // output extent of an input extent
@@ -160,13 +209,13 @@ int sgx_wgrad2_launch(int geo, const Wg2Plan& p, const void* kside, const void* 
 // recorded on the launch stream itself; records are resolved to kernel names and milliseconds by sgx_prof_get.
 extern int sgx_prof_mode;                                  // 0 off, 1 every kernel, 2 only sgx_prof_only_fn
 extern const void* sgx_prof_only_fn;
-void sgx_prof_begin(const void* fn, hipStream_t st, int* slot);
+void sgx_prof_begin(const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t st, int* slot);
 void sgx_prof_end(int slot, hipStream_t st);
 void sgx_prof_note(double flops, double bytes, const char* fmt, ...);   // describes the NEXT launch of this thread
 template <typename K, typename... Args>
 static inline void sgx_launch(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
     int slot = -1;
-    if (sgx_prof_mode) sgx_prof_begin(reinterpret_cast<const void*>(kern), st, &slot);
+    if (sgx_prof_mode) sgx_prof_begin(reinterpret_cast<const void*>(kern), grid, block, lds, st, &slot);
     kern<<<grid, block, lds, st>>>(args...);
     if (slot >= 0) sgx_prof_end(slot, st);
 }

@@ -1,21 +1,18 @@
 // The image-side 1x1 convolutions and the uint8 ingest for images that are not RGB: J = 1, 2, 4 image channels (grayscale, gray + alpha,
 // RGBA) and J = 8 (the conditional discriminator's [RGBA image, label embedding] input).  The 3-channel kernels of pointwise.hip stay what
-// they are; these are their J-templated siblings with the same launch geometry (rgb_in1_launch / rgb_out_launch and the comments there):
+// they are; these are their J-templated siblings with the same launch geometry (rgb_in_run / rgb_out_launch and the comments there):
 // a grid-stride loop kernel for small launches, short-lived blocks that move one 16-byte vector of y / x per thread per trip above a
 // size threshold, two-stage fixed-order fp64 partials for the weight gradient.  The image side of a pixel is ONE load of 4 J bytes (J = 8:
 // two 16-byte loads); with J = 1 the lanes that share a pixel read the same dword (one request, broadcast), not a wider vector each.
 #include "common.h"
 
-static inline unsigned img_grid_for(size_t nvec) {                   // the capped grid of the loop kernels, as pointwise.hip's grid_for
-    size_t g = (nvec + 255) / 256;
-    static const size_t cap = [] { const long v = sgx_env_int("SGX_GRID_CAP", 8192); return (size_t)(v > 0 ? v : 0x7fffffffL); }();
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
 // A/B switch and size threshold of the short-lived-block kernels: 0 = the loop kernels always, else the smallest number of 16-byte
 // vectors of y (img_in) / of pixels (img_out) that takes them.  Measured: tools/imgconv_probe.py --sweep, see img_in_run below.
 SGX_SWITCH(img1_min, "SGX_IMG1_MIN", 65536)
+// The image channel counts the convolutions are instantiated for, and those of the uint8 ingest: sgx_by_int<IMG_JS>(J, f) calls f with J
+// as a compile-time constant (common.h); the entry points have refused every other J before.
+#define IMG_JS 1, 2, 4, 8
+#define IMG_U8_JS 1, 2, 3, 4
 
 template <int J>
 __device__ __forceinline__ void img_load(const float* __restrict__ p, float (&v)[J]) {
@@ -51,7 +48,7 @@ template <typename T, int J>
 __global__ void img_in_kernel(const float* __restrict__ img, const float* __restrict__ w, int sj, int sc, float wscale,
                               const float* __restrict__ bias, T* __restrict__ y, size_t npix, int C) {
     constexpr int VE = VecTraits<T>::VE;
-    const int cv = C / VE;                                   // divides the grid stride (img_in_grid)
+    const int cv = C / VE;                                   // divides the grid stride (grid_for_hoisted)
     const size_t nvec = npix * cv;
     const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int c0 = (int)(i0 % cv) * VE;                      // the thread's channel group never changes: hoist its weights
@@ -113,17 +110,11 @@ __global__ __launch_bounds__(256) void img_in1_kernel(const float* __restrict__ 
         VecTraits<T>::store(y + (size_t)i * VE, v);
     }
 }
-// the loop kernel hoists its channel group's weights, so the grid stride (256 * blocks) must be a multiple of cv
-static inline unsigned img_in_grid(size_t nvec, int cv) {
-    unsigned g = img_grid_for(nvec);
-    if (256 % cv != 0) g = (g + cv - 1) / cv * cv;
-    return g;
-}
 template <typename T, int J>
 static void img_in_run(const float* img, const float* w, int sj, int sc, float wscale, const float* bias, T* y, size_t npix, int C, hipStream_t st) {
     constexpr int VE = VecTraits<T>::VE;
     const size_t nvec = npix * (C / VE);
-    // The threshold is rgb_in1_launch's, 65536 vectors.  Measured for this kernel (tools/imgconv_probe.py --sweep, profiles/imgconv_probe.json:
+    // The threshold is rgb_in_run's, 65536 vectors.  Measured for this kernel (tools/imgconv_probe.py --sweep, profiles/imgconv_probe.json:
     // bf16, C = 16, J = 4, launches timed alone with events; loop kernel / short-lived blocks, us): 131072 pixels (262144 vectors) 10.5 / 9.4,
     // 262144 px 14.8 / 9.9, 1M px 43.0 / 13.6, 4M px 82.5 / 41.3; at 65536 pixels and below both read 8-9 us, the floor of an event-timed launch,
     // so the probe cannot place the crossover more finely than "at or below 131072 vectors" and the 3-channel kernel's figure stands.
@@ -133,17 +124,7 @@ static void img_in_run(const float* img, const float* w, int sj, int sc, float w
         hipLaunchKernelGGL((img_in1_kernel<T, J>), dim3((unsigned)((nvec + 1023) / 1024)), dim3(256), (size_t)(J + 1) * C * sizeof(float), st, img, w, sj, sc,
                            wscale, bias, y, (unsigned)nvec, C);
     else
-        hipLaunchKernelGGL((img_in_kernel<T, J>), dim3(img_in_grid(nvec, C / VE)), dim3(256), 0, st, img, w, sj, sc, wscale, bias, y, npix, C);
-}
-template <typename T>
-static bool img_in_j(const float* img, const float* w, int J, int sj, int sc, float wscale, const float* bias, T* y, size_t npix, int C, hipStream_t st) {
-    switch (J) {
-    case 1: img_in_run<T, 1>(img, w, sj, sc, wscale, bias, y, npix, C, st); return true;
-    case 2: img_in_run<T, 2>(img, w, sj, sc, wscale, bias, y, npix, C, st); return true;
-    case 4: img_in_run<T, 4>(img, w, sj, sc, wscale, bias, y, npix, C, st); return true;
-    case 8: img_in_run<T, 8>(img, w, sj, sc, wscale, bias, y, npix, C, st); return true;
-    }
-    return false;
+        hipLaunchKernelGGL((img_in_kernel<T, J>), dim3(grid_for_hoisted(nvec, C / VE)), dim3(256), 0, st, img, w, sj, sc, wscale, bias, y, npix, C);
 }
 static inline bool img_aligned(const void* p, int J) { return (reinterpret_cast<uintptr_t>(p) & (size_t)(4 * (J > 4 ? 4 : J) - 1)) == 0; }
 
@@ -152,14 +133,15 @@ extern "C" int sgx_img_in(const float* img, const float* w, int J, int sj, int s
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(img && w && y && npix > 0, SGX_EINVAL, "img_in: null argument");
     SGX_REQUIRE(J == 1 || J == 2 || J == 4 || J == 8, SGX_EUNSUPPORTED, "img_in: J=%d (1, 2, 4 or 8 image channels)", J);
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "img_in: bad dtype");
-    SGX_REQUIRE(C > 0 && C % (dtype == SGX_F32 ? 4 : 8) == 0, SGX_EUNSUPPORTED, "img_in: C=%d (whole 16-byte channel vectors)", C);
-    SGX_REQUIRE(img_aligned(img, J) && (reinterpret_cast<uintptr_t>(y) & 15) == 0, SGX_EINVAL, "img_in: misaligned image or output");
-    SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "img_in J%d %zux%d", J, npix, C);
-    if (dtype == SGX_F32) img_in_j<float>(img, w, J, sj, sc, wscale, bias, (float*)y, npix, C, st);
-    else img_in_j<bf16_t>(img, w, J, sj, sc, wscale, bias, (bf16_t*)y, npix, C, st);
-    SGX_LAUNCH_CHECK("img_in");
-    return 0;
+    return sgx_by_dtype(dtype, "img_in", [&](auto t) -> int {
+        using T = decltype(t);
+        SGX_REQUIRE(C > 0 && C % VecTraits<T>::VE == 0, SGX_EUNSUPPORTED, "img_in: C=%d (whole 16-byte channel vectors)", C);
+        SGX_REQUIRE(img_aligned(img, J) && sgx_aligned16(y), SGX_EINVAL, "img_in: misaligned image or output");
+        SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + sgx_esize(dtype) * C), "img_in J%d %zux%d", J, npix, C);
+        sgx_by_int<IMG_JS>(J, [&](auto j) { img_in_run<T, j()>(img, w, sj, sc, wscale, bias, as<T>(y), npix, C, st); });
+        SGX_LAUNCH_CHECK("img_in");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- activations -> image: img[p][j] = bias[j] + sum_c x[p][c] (wscale W(j,c))
@@ -282,33 +264,26 @@ static void img_out_run(const T* x, const float* w, int sj, int sc, float wscale
         const unsigned ppb4 = (unsigned)(256 / lpp) * 4;
         hipLaunchKernelGGL((img_out1_kernel<T, J>), dim3((unsigned)((npix + ppb4 - 1) / ppb4)), dim3(256), sh, st, x, w, sj, sc, wscale, bias, img, (unsigned)npix, C, lpp);
     } else {
-        hipLaunchKernelGGL((img_out_kernel<T, J>), dim3(img_grid_for(npix * lpp)), dim3(256), sh, st, x, w, sj, sc, wscale, bias, img, npix, C, lpp);
+        hipLaunchKernelGGL((img_out_kernel<T, J>), dim3(grid_for(npix * lpp)), dim3(256), sh, st, x, w, sj, sc, wscale, bias, img, npix, C, lpp);
     }
-}
-template <typename T>
-static void img_out_j(const T* x, const float* w, int J, int sj, int sc, float wscale, const float* bias, float* img, size_t npix, int C, int lpp, hipStream_t st) {
-    if (J == 1) img_out_run<T, 1>(x, w, sj, sc, wscale, bias, img, npix, C, lpp, st);
-    else if (J == 2) img_out_run<T, 2>(x, w, sj, sc, wscale, bias, img, npix, C, lpp, st);
-    else if (J == 4) img_out_run<T, 4>(x, w, sj, sc, wscale, bias, img, npix, C, lpp, st);
-    else img_out_run<T, 8>(x, w, sj, sc, wscale, bias, img, npix, C, lpp, st);
 }
 extern "C" int sgx_img_out(const void* x, const float* w, int J, int sj, int sc, float wscale, const float* bias, float* img, size_t npix, int C, int dtype,
                            void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(x && w && img && npix > 0, SGX_EINVAL, "img_out: null argument");
     SGX_REQUIRE(J == 1 || J == 2 || J == 4 || J == 8, SGX_EUNSUPPORTED, "img_out: J=%d (1, 2, 4 or 8 image channels)", J);
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "img_out: bad dtype");
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE(C > 0 && C % ve == 0 && (long)J * C <= 8192, SGX_EUNSUPPORTED, "img_out: C=%d (whole 16-byte channel vectors, J * C <= 8192: the weights' 32 KB of LDS)", C);
-    int lpp = C / ve;
-    if (lpp > 16) lpp = 16;
-    SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "img_out: C=%d (min(vectors per pixel, 16) must be a power of two)", C);
-    SGX_REQUIRE(img_aligned(img, J) && (reinterpret_cast<uintptr_t>(x) & 15) == 0, SGX_EINVAL, "img_out: misaligned image or input");
-    SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "img_out J%d %zux%d", J, npix, C);
-    if (dtype == SGX_F32) img_out_j<float>((const float*)x, w, J, sj, sc, wscale, bias, img, npix, C, lpp, st);
-    else img_out_j<bf16_t>((const bf16_t*)x, w, J, sj, sc, wscale, bias, img, npix, C, lpp, st);
-    SGX_LAUNCH_CHECK("img_out");
-    return 0;
+    return sgx_by_dtype(dtype, "img_out", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C > 0 && C % VE == 0 && (long)J * C <= 8192, SGX_EUNSUPPORTED, "img_out: C=%d (whole 16-byte channel vectors, J * C <= 8192: the weights' 32 KB of LDS)", C);
+        const int lpp = C / VE > 16 ? 16 : C / VE;
+        SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "img_out: C=%d (min(vectors per pixel, 16) must be a power of two)", C);
+        SGX_REQUIRE(img_aligned(img, J) && sgx_aligned16(x), SGX_EINVAL, "img_out: misaligned image or input");
+        SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + sgx_esize(dtype) * C), "img_out J%d %zux%d", J, npix, C);
+        sgx_by_int<IMG_JS>(J, [&](auto j) { img_out_run<T, j()>(as<T>(x), w, sj, sc, wscale, bias, img, npix, C, lpp, st); });
+        SGX_LAUNCH_CHECK("img_out");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- weight gradient: dW(j,c) = wscale sum_p img[p][j] f[p][c]
@@ -390,38 +365,31 @@ extern "C" size_t sgx_img_wgrad_ws_bytes(size_t npix, int J, int C) {
     (void)npix;
     return (size_t)IMG_WGRAD_BLOCKS * (size_t)(J > 0 ? J : 1) * (size_t)(C > 0 ? C : 1) * sizeof(double);
 }
-template <typename T>
-static void img_wgrad_j(const T* f, const float* img, double* ws, int J, size_t npix, int C, int nblk, hipStream_t st) {
-    constexpr int VE = VecTraits<T>::VE;
-    const size_t sh = (size_t)256 * ((J > 4 ? 4 : J) * VE + 1) * sizeof(float);
-    switch (J) {
-    case 1: hipLaunchKernelGGL((img_wgrad_stage1<T, 1>), dim3(nblk), dim3(256), sh, st, f, img, ws, npix, C); break;
-    case 2: hipLaunchKernelGGL((img_wgrad_stage1<T, 2>), dim3(nblk), dim3(256), sh, st, f, img, ws, npix, C); break;
-    case 4: hipLaunchKernelGGL((img_wgrad_stage1<T, 4>), dim3(nblk), dim3(256), sh, st, f, img, ws, npix, C); break;
-    default: hipLaunchKernelGGL((img_wgrad_stage1<T, 8>), dim3(nblk), dim3(256), sh, st, f, img, ws, npix, C); break;
-    }
-}
 extern "C" int sgx_img_wgrad(const float* img, const void* f, float* dw, int J, int sj, int sc, float wscale, void* ws, size_t ws_bytes, size_t npix, int C,
                              int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(img && f && dw && ws && npix > 0, SGX_EINVAL, "img_wgrad: null argument");
     SGX_REQUIRE(J == 1 || J == 2 || J == 4 || J == 8, SGX_EUNSUPPORTED, "img_wgrad: J=%d (1, 2, 4 or 8 image channels)", J);
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "img_wgrad: bad dtype");
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE(C > 0 && C % ve == 0 && C / ve <= 256, SGX_EUNSUPPORTED, "img_wgrad: C=%d (whole 16-byte channel vectors, at most 256 of them)", C);
-    SGX_REQUIRE(ws_bytes >= sgx_img_wgrad_ws_bytes(npix, J, C), SGX_EWORKSPACE, "img_wgrad: workspace");
-    SGX_REQUIRE(img_aligned(img, J) && (reinterpret_cast<uintptr_t>(f) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 7) == 0, SGX_EINVAL,
-                "img_wgrad: misaligned image, gradient or workspace");
-    SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "img_wgrad J%d %zux%d", J, npix, C);
-    int nblk = (int)((npix + 63) / 64);
-    if (nblk > IMG_WGRAD_BLOCKS) nblk = IMG_WGRAD_BLOCKS;
-    if (nblk < 1) nblk = 1;
-    if (dtype == SGX_F32) img_wgrad_j<float>((const float*)f, img, (double*)ws, J, npix, C, nblk, st);
-    else img_wgrad_j<bf16_t>((const bf16_t*)f, img, (double*)ws, J, npix, C, nblk, st);
-    SGX_LAUNCH_CHECK("img_wgrad_stage1");
-    hipLaunchKernelGGL(img_wgrad_stage2, dim3((J * C + 3) / 4), dim3(256), 0, st, (const double*)ws, dw, nblk, J, C, sj, sc, wscale);
-    SGX_LAUNCH_CHECK("img_wgrad_stage2");
-    return 0;
+    return sgx_by_dtype(dtype, "img_wgrad", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C > 0 && C % VE == 0 && C / VE <= 256, SGX_EUNSUPPORTED, "img_wgrad: C=%d (whole 16-byte channel vectors, at most 256 of them)", C);
+        SGX_REQUIRE(ws_bytes >= sgx_img_wgrad_ws_bytes(npix, J, C), SGX_EWORKSPACE, "img_wgrad: workspace");
+        SGX_REQUIRE(img_aligned(img, J) && sgx_aligned16(f) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0, SGX_EINVAL,
+                    "img_wgrad: misaligned image, gradient or workspace");
+        SGX_NOTE(2.0 * J * npix * C, npix * (4.0 * J + sgx_esize(dtype) * C), "img_wgrad J%d %zux%d", J, npix, C);
+        int nblk = (int)((npix + 63) / 64);
+        if (nblk > IMG_WGRAD_BLOCKS) nblk = IMG_WGRAD_BLOCKS;
+        if (nblk < 1) nblk = 1;
+        const size_t sh = (size_t)256 * ((J > 4 ? 4 : J) * VE + 1) * sizeof(float);
+        sgx_by_int<IMG_JS>(J, [&](auto j) {
+            hipLaunchKernelGGL((img_wgrad_stage1<T, j()>), dim3(nblk), dim3(256), sh, st, as<T>(f), img, (double*)ws, npix, C);
+        });
+        SGX_LAUNCH_CHECK("img_wgrad_stage1");
+        hipLaunchKernelGGL(img_wgrad_stage2, dim3((J * C + 3) / 4), dim3(256), 0, st, (const double*)ws, dw, nblk, J, C, sj, sc, wscale);
+        SGX_LAUNCH_CHECK("img_wgrad_stage2");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- uint8 images with J channels -> normalised NHWC activations
@@ -495,33 +463,27 @@ __global__ void images_u8_c_px_kernel(const unsigned char* __restrict__ src, T* 
 template <typename T, int J>
 static void images_u8_c_run(const unsigned char* s, T* d, const int* flip, int B, int H, int W, int chw, hipStream_t st) {
     if (W % 4 == 0) {
-        const unsigned g = img_grid_for((size_t)B * H * (W / 4));
+        const unsigned g = grid_for((size_t)B * H * (W / 4));
         if (chw) hipLaunchKernelGGL((images_u8_c_kernel<T, J, true>), dim3(g), dim3(256), 0, st, s, d, flip, B, H, W);
         else hipLaunchKernelGGL((images_u8_c_kernel<T, J, false>), dim3(g), dim3(256), 0, st, s, d, flip, B, H, W);
     } else {
-        const unsigned g = img_grid_for((size_t)B * H * W);
+        const unsigned g = grid_for((size_t)B * H * W);
         if (chw) hipLaunchKernelGGL((images_u8_c_px_kernel<T, J, true>), dim3(g), dim3(256), 0, st, s, d, flip, B, H, W);
         else hipLaunchKernelGGL((images_u8_c_px_kernel<T, J, false>), dim3(g), dim3(256), 0, st, s, d, flip, B, H, W);
     }
-}
-template <typename T>
-static void images_u8_c_j(const unsigned char* s, T* d, const int* flip, int B, int H, int W, int J, int chw, hipStream_t st) {
-    if (J == 1) images_u8_c_run<T, 1>(s, d, flip, B, H, W, chw, st);
-    else if (J == 2) images_u8_c_run<T, 2>(s, d, flip, B, H, W, chw, st);
-    else if (J == 3) images_u8_c_run<T, 3>(s, d, flip, B, H, W, chw, st);
-    else images_u8_c_run<T, 4>(s, d, flip, B, H, W, chw, st);
 }
 extern "C" int sgx_images_u8_to_nhwc_c(const void* src, void* dst, const int* flip, int B, int H, int W, int J, int src_chw, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(src && dst && B > 0 && H > 0 && W > 0, SGX_EINVAL, "images_u8_to_nhwc_c: bad arguments (B%d %dx%d)", B, H, W);
     SGX_REQUIRE(J >= 1 && J <= 4, SGX_EUNSUPPORTED, "images_u8_to_nhwc_c: J=%d (1 to 4 channels)", J);
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "images_u8_to_nhwc_c: bad dtype");
-    SGX_REQUIRE(W % 4 != 0 || ((reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0), SGX_EINVAL,
-                "images_u8_to_nhwc_c: misaligned source or output");
-    SGX_NOTE(0.0, (1.0 + (dtype == SGX_F32 ? 4.0 : 2.0)) * J * B * H * W, "images_u8 J%d B%d %dx%d", J, B, H, W);
-    const auto* s = static_cast<const unsigned char*>(src);
-    if (dtype == SGX_F32) images_u8_c_j<float>(s, (float*)dst, flip, B, H, W, J, src_chw, st);
-    else images_u8_c_j<bf16_t>(s, (bf16_t*)dst, flip, B, H, W, J, src_chw, st);
-    SGX_LAUNCH_CHECK("images_u8_c_kernel");
-    return 0;
+    return sgx_by_dtype(dtype, "images_u8_to_nhwc_c", [&](auto t) -> int {
+        using T = decltype(t);
+        SGX_REQUIRE(W % 4 != 0 || ((reinterpret_cast<uintptr_t>(src) & 3) == 0 && sgx_aligned16(dst)), SGX_EINVAL,
+                    "images_u8_to_nhwc_c: misaligned source or output");
+        SGX_NOTE(0.0, (1.0 + sgx_esize(dtype)) * J * B * H * W, "images_u8 J%d B%d %dx%d", J, B, H, W);
+        const auto* s = static_cast<const unsigned char*>(src);
+        sgx_by_int<IMG_U8_JS>(J, [&](auto j) { images_u8_c_run<T, j()>(s, as<T>(dst), flip, B, H, W, src_chw, st); });
+        SGX_LAUNCH_CHECK("images_u8_c_kernel");
+        return 0;
+    });
 }

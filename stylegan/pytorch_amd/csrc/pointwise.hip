@@ -1,27 +1,9 @@
 // HBM-bound pieces of the StyleGAN layers (NHWC): bias/activation, LeakyReLU backward, fade-in lerp, depthwise blur,
-// 2x2 pooling, nearest upsample, per-channel sums, 1x1 RGB convolutions.  One 16-byte vector per lane per access;
-// grid-stride loops capped at 256 CUs x 8 blocks.
+// 2x2 pooling, nearest upsample, per-channel sums, 1x1 RGB convolutions.  One 16-byte vector per lane per access.
+// Launch layer: an entry point checks its arguments, sgx_by_dtype (common.h) turns dtype into the element type T once, and every kernel
+// template has one hipLaunchKernelGGL site per literal instantiation, spelled with T.  Grids are grid_for (grid-stride loops under the
+// SGX_GRID_CAP block cap) or grid_all (one trip per thread) of common.h; the A/B switches are SGX_SWITCH accessors.
 #include "common.h"
-
-static inline unsigned grid_for(size_t nvec, int block = 256) {
-    size_t g = (nvec + block - 1) / block;
-    static const size_t cap = [] { const char* e = getenv("SGX_GRID_CAP"); const long v = e ? atol(e) : 8192; return (size_t)(v > 0 ? v : 0x7fffffffL); }();
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
-// The grid of a pass whose threads have NO per-thread setup worth amortising (pure elementwise kernels, the blur's strips): one trip of the
-// kernel's grid-stride loop per thread.  Round 6, tools/stream_probe.hip + the step's layer tables with SGX_GRID_CAP=0: a read + write stream
-// runs at 6.1-6.2 TB/s as short-lived blocks against 5.0-5.1 under the 8192-block cap above (lrelu_bwd_bits 214 -> 184 us, lrelu_bwd 148 ->
-// 126, up2+add 164 -> 146, the blurs -2..4 %); kernels that hoist weights per thread (rgb_in / rgb_out / fade_rgb_bwd2) lose and keep the cap.
-// SGX_GRID_ALL_CAP (A/B): the cap of these launches, default none.
-static inline unsigned grid_all(size_t nvec, int block = 256) {
-    size_t g = (nvec + block - 1) / block;
-    static const size_t cap = [] { const char* e = getenv("SGX_GRID_ALL_CAP"); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : 0x7fffffffL); }();
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
 
 // ---------------------------------------------------------------- y = act(x + bias[c])
 template <typename T>
@@ -51,23 +33,21 @@ __global__ void bias_act_scalar_kernel(const float* __restrict__ x, const float*
 extern "C" int sgx_bias_act(const void* x, const float* bias, float bscale, void* y, size_t npix, int C, int act, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(act >= SGX_ACT_NONE && act <= SGX_ACT_RELU, SGX_EINVAL, "bias_act: activation %d", act);
-    SGX_NOTE(0.0, 2.0 * (dtype == SGX_F32 ? 4.0 : 2.0) * npix * C, "bias_act %zux%d", npix, C);
+    SGX_NOTE(0.0, 2.0 * sgx_esize(dtype) * npix * C, "bias_act %zux%d", npix, C);
     if (dtype == SGX_F32 && C % 4 != 0) {                    // e.g. the [B,1] discriminator output
         hipLaunchKernelGGL(bias_act_scalar_kernel, dim3(grid_for(npix * C)), dim3(256), 0, st, (const float*)x, bias, bscale, (float*)y, npix * C, C, act);
         SGX_LAUNCH_CHECK("bias_act_scalar");
         return 0;
     }
-    if (dtype == SGX_F32) {
-        SGX_REQUIRE(C % 4 == 0, SGX_EUNSUPPORTED, "bias_act: C %% 4");
-        size_t nvec = npix * C / 4;
-        hipLaunchKernelGGL(bias_act_kernel<float>, dim3(grid_all(nvec)), dim3(256), 0, st, (const float*)x, bias, bscale, (float*)y, nvec, C, act);
-    } else {
-        SGX_REQUIRE(C % 8 == 0, SGX_EUNSUPPORTED, "bias_act: C %% 8");
-        size_t nvec = npix * C / 8;
-        hipLaunchKernelGGL(bias_act_kernel<bf16_t>, dim3(grid_all(nvec)), dim3(256), 0, st, (const bf16_t*)x, bias, bscale, (bf16_t*)y, nvec, C, act);
-    }
-    SGX_LAUNCH_CHECK("bias_act");
-    return 0;
+    return sgx_by_dtype(dtype, "bias_act", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C % VE == 0, SGX_EUNSUPPORTED, "bias_act: C %% %d", VE);
+        const size_t nvec = npix * C / VE;
+        hipLaunchKernelGGL(bias_act_kernel<T>, dim3(grid_all(nvec)), dim3(256), 0, st, as<T>(x), bias, bscale, as<T>(y), nvec, C, act);
+        SGX_LAUNCH_CHECK("bias_act");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- dx = scale * dy * (y > 0 ? 1 : slope)   (slope 0.2: LeakyReLU; 0: ReLU)
@@ -90,16 +70,15 @@ __global__ void lrelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__
 extern "C" int sgx_lrelu_bwd(const void* dy, const void* y, void* dx, size_t n, float slope, float scale, const float* scale_dev, int dtype,
                              void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    SGX_NOTE(0.0, 3.0 * (dtype == SGX_F32 ? 4.0 : 2.0) * n, "lrelu_bwd %zu", n);
-    if (dtype == SGX_F32) {
-        SGX_REQUIRE(n % 4 == 0, SGX_EUNSUPPORTED, "lrelu_bwd: n %% 4");
-        hipLaunchKernelGGL(lrelu_bwd_kernel<float>, dim3(grid_all(n / 4)), dim3(256), 0, st, (const float*)dy, (const float*)y, (float*)dx, n / 4, slope, scale, scale_dev);
-    } else {
-        SGX_REQUIRE(n % 8 == 0, SGX_EUNSUPPORTED, "lrelu_bwd: n %% 8");
-        hipLaunchKernelGGL(lrelu_bwd_kernel<bf16_t>, dim3(grid_all(n / 8)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dx, n / 8, slope, scale, scale_dev);
-    }
-    SGX_LAUNCH_CHECK("lrelu_bwd");
-    return 0;
+    SGX_NOTE(0.0, 3.0 * sgx_esize(dtype) * n, "lrelu_bwd %zu", n);
+    return sgx_by_dtype(dtype, "lrelu_bwd", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(n % VE == 0, SGX_EUNSUPPORTED, "lrelu_bwd: n %% %d", VE);
+        hipLaunchKernelGGL(lrelu_bwd_kernel<T>, dim3(grid_all(n / VE)), dim3(256), 0, st, as<T>(dy), as<T>(y), as<T>(dx), n / VE, slope, scale, scale_dev);
+        SGX_LAUNCH_CHECK("lrelu_bwd");
+        return 0;
+    });
 }
 
 // the same with the activation given as SIGN BITS (bits[i] = the signs of the 8 channels of vector i, as sgx_conv3x3_signbits /
@@ -121,6 +100,7 @@ __global__ void lrelu_bwd_bits_kernel(const bf16_t* __restrict__ dy, const unsig
 }
 extern "C" int sgx_lrelu_bwd_bits(const void* dy, const void* bits, void* dx, size_t n, float slope, float scale, const float* scale_dev, int dtype,
                                   void* stream) {
+    SGX_REQUIRE(sgx_dtype_ok(dtype), SGX_EINVAL, "lrelu_bwd_bits: dtype %d", dtype);
     SGX_REQUIRE(dtype == SGX_BF16 && n % 8 == 0, SGX_EUNSUPPORTED, "lrelu_bwd_bits: bf16, n %% 8 == 0");
     SGX_REQUIRE(dy && bits && dx, SGX_EINVAL, "lrelu_bwd_bits: null argument");
     SGX_NOTE(0.0, 4.125 * n, "lrelu_bwd_bits %zu", n);
@@ -244,18 +224,26 @@ __global__ __launch_bounds__(256) void fade_rgb_bwd_finish(const double* __restr
     }
 }
 extern "C" size_t sgx_fade_rgb_bwd_ws_bytes(size_t npix, int C) { (void)npix; return (size_t)FRB_BLOCKS * 4 * C * sizeof(double); }
+// blocks of fade_rgb_bwd_kernel = the partials fade_rgb_bwd_finish sums: one per 8 x 256 / (C / 8) pixels, at most FRB_BLOCKS
+static int frb_blocks(size_t npix, int C) {
+    const size_t per = (size_t)(256 / (C / 8)) * 8, n = (npix + per - 1) / per;
+    return n > FRB_BLOCKS ? FRB_BLOCKS : (n < 1 ? 1 : (int)n);
+}
+static int frb_finish(const double* part, int nblk, int C, float ws, float bs, float beta, const float* ab_dev, float* dwr, float* drb, int acc, hipStream_t st) {
+    hipLaunchKernelGGL(fade_rgb_bwd_finish, dim3((unsigned)((4 * C + 3) / 4)), dim3(256), 0, st, part, dwr, drb, nblk, C, ws, bs, beta, ab_dev, acc);
+    SGX_LAUNCH_CHECK("fade_rgb_bwd_finish");
+    return 0;
+}
 extern "C" int sgx_fade_rgb_bwd(const void* g, const void* bits, const float* pimg, const float* wr, float ws, float bs, float alpha, float beta,
                                 const float* ab_dev, void* gy, float* dwr, float* drb, int acc, float* gpimg, void* wsbuf, size_t ws_bytes, size_t npix, int C,
                                 int dtype, void* stream) {
+    SGX_REQUIRE(sgx_dtype_ok(dtype), SGX_EINVAL, "fade_rgb_bwd: dtype %d", dtype);
     SGX_REQUIRE(dtype == SGX_BF16 && (C == 32 || C == 64 || C == 128), SGX_EUNSUPPORTED, "fade_rgb_bwd: bf16, C in {32, 64, 128} (C=%d dtype %d)", C, dtype);
     SGX_REQUIRE(g && bits && pimg && wr && gy && wsbuf && npix > 0, SGX_EINVAL, "fade_rgb_bwd: null argument");
     SGX_REQUIRE(ws_bytes >= sgx_fade_rgb_bwd_ws_bytes(npix, C), SGX_EWORKSPACE, "fade_rgb_bwd: workspace");
     SGX_NOTE(8.0 * npix * C, npix * (4.125 * C + 12.0 + (gpimg ? 12.0 : 0.0)), "fade_rgb_bwd %zux%d", npix, C);
     hipStream_t st = (hipStream_t)stream;
-    const int ppi = 256 / (C / 8);
-    long nblk = (long)((npix + (size_t)ppi * 8 - 1) / ((size_t)ppi * 8));
-    if (nblk > FRB_BLOCKS) nblk = FRB_BLOCKS;
-    if (nblk < 1) nblk = 1;
+    const int nblk = frb_blocks(npix, C);
     const bf16_t* gp = static_cast<const bf16_t*>(g);
     const unsigned char* bp = static_cast<const unsigned char*>(bits);
     bf16_t* yp = static_cast<bf16_t*>(gy);
@@ -265,11 +253,7 @@ extern "C" int sgx_fade_rgb_bwd(const void* g, const void* bits, const float* pi
     else if (C == 64) hipLaunchKernelGGL(fade_rgb_bwd_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st, gp, bp, pimg, wr, ws, alpha, beta, ab_dev, yp, gpimg, part, npix, nt);
     else hipLaunchKernelGGL(fade_rgb_bwd_kernel<16>, dim3((unsigned)nblk), dim3(256), 0, st, gp, bp, pimg, wr, ws, alpha, beta, ab_dev, yp, gpimg, part, npix, nt);
     SGX_LAUNCH_CHECK("fade_rgb_bwd_kernel");
-    if (dwr || drb) {
-        hipLaunchKernelGGL(fade_rgb_bwd_finish, dim3((unsigned)((4 * C + 3) / 4)), dim3(256), 0, st, part, dwr, drb, (int)nblk, C, ws, bs, beta, ab_dev, acc);
-        SGX_LAUNCH_CHECK("fade_rgb_bwd_finish");
-    }
-    return 0;
+    return (dwr || drb) ? frb_finish(part, nblk, C, ws, bs, beta, ab_dev, dwr, drb, acc, st) : 0;
 }
 // The parameter-gradient half of sgx_fade_rgb_bwd on its own: sums the block partials a call with dwr = drb = NULL left in `wsbuf` and
 // writes / accumulates from_rgb's gradients.  The caller orders it behind that call and may run it on another stream -- the one every
@@ -279,15 +263,9 @@ extern "C" int sgx_fade_rgb_bwd_finish(const void* wsbuf, size_t ws_bytes, size_
     SGX_REQUIRE(C == 32 || C == 64 || C == 128, SGX_EUNSUPPORTED, "fade_rgb_bwd_finish: C in {32, 64, 128} (C=%d)", C);
     SGX_REQUIRE(wsbuf && npix > 0 && (dwr || drb), SGX_EINVAL, "fade_rgb_bwd_finish: null argument");
     SGX_REQUIRE(ws_bytes >= sgx_fade_rgb_bwd_ws_bytes(npix, C), SGX_EWORKSPACE, "fade_rgb_bwd_finish: workspace");
-    const int ppi = 256 / (C / 8);
-    long nblk = (long)((npix + (size_t)ppi * 8 - 1) / ((size_t)ppi * 8));      // as sgx_fade_rgb_bwd
-    if (nblk > FRB_BLOCKS) nblk = FRB_BLOCKS;
-    if (nblk < 1) nblk = 1;
+    const int nblk = frb_blocks(npix, C);
     SGX_NOTE(0.0, (double)nblk * 4 * C * sizeof(double), "fade_rgb_bwd_finish C%d", C);
-    hipLaunchKernelGGL(fade_rgb_bwd_finish, dim3((unsigned)((4 * C + 3) / 4)), dim3(256), 0, (hipStream_t)stream, static_cast<const double*>(wsbuf), dwr, drb,
-                       (int)nblk, C, ws, bs, beta, ab_dev, acc);
-    SGX_LAUNCH_CHECK("fade_rgb_bwd_finish");
-    return 0;
+    return frb_finish(static_cast<const double*>(wsbuf), nblk, C, ws, bs, beta, ab_dev, dwr, drb, acc, (hipStream_t)stream);
 }
 
 // The adjoint of sgx_fade_rgb_bwd's data half -- what the R1 double backward needs of the newest block's tail -- in ONE pass:
@@ -334,6 +312,7 @@ __global__ __launch_bounds__(256) void fade_rgb_bwd2_kernel(const bf16_t* __rest
 }
 extern "C" int sgx_fade_rgb_bwd2(const void* ggy, const float* ggp, const void* bits, const float* wr, float ws, float alpha, float beta, const float* ab_dev,
                                  void* out, size_t npix, int C, int dtype, void* stream) {
+    SGX_REQUIRE(sgx_dtype_ok(dtype), SGX_EINVAL, "fade_rgb_bwd2: dtype %d", dtype);
     SGX_REQUIRE(dtype == SGX_BF16 && (C == 32 || C == 64 || C == 128), SGX_EUNSUPPORTED, "fade_rgb_bwd2: bf16, C in {32, 64, 128} (C=%d dtype %d)", C, dtype);
     SGX_REQUIRE((ggy || ggp) && wr && out && npix > 0 && (!ggy || bits), SGX_EINVAL, "fade_rgb_bwd2: null argument");
     SGX_REQUIRE(ab_dev || beta == 1.0f, SGX_EUNSUPPORTED, "fade_rgb_bwd2: a host beta other than 1 rides in ws (as the forward's)");
@@ -377,17 +356,16 @@ __global__ void axpby_kernel(const T* __restrict__ a, const T* __restrict__ b, T
 static int axpby_launch(const void* a, const void* b, void* out, float alpha, float beta, const float* alpha_dev, const float* beta_dev,
                         size_t n, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    SGX_NOTE(0.0, (b ? 3.0 : 2.0) * (dtype == SGX_F32 ? 4.0 : 2.0) * n, "axpby %zu", n);
-    if (n == 0) return 0;
-    if (dtype == SGX_F32) {
-        size_t nvec = (n + 3) / 4;
-        hipLaunchKernelGGL(axpby_kernel<float>, dim3(grid_all(nvec)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, alpha, beta, alpha_dev, beta_dev, nvec, n);
-    } else {
-        size_t nvec = (n + 7) / 8;
-        hipLaunchKernelGGL(axpby_kernel<bf16_t>, dim3(grid_all(nvec)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, alpha, beta, alpha_dev, beta_dev, nvec, n);
-    }
-    SGX_LAUNCH_CHECK("axpby");
-    return 0;
+    SGX_NOTE(0.0, (b ? 3.0 : 2.0) * sgx_esize(dtype) * n, "axpby %zu", n);
+    return sgx_by_dtype(dtype, "axpby", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        if (n == 0) return 0;
+        const size_t nvec = (n + VE - 1) / VE;
+        hipLaunchKernelGGL(axpby_kernel<T>, dim3(grid_all(nvec)), dim3(256), 0, st, as<T>(a), as<T>(b), as<T>(out), alpha, beta, alpha_dev, beta_dev, nvec, n);
+        SGX_LAUNCH_CHECK("axpby");
+        return 0;
+    });
 }
 extern "C" int sgx_axpby(const void* a, const void* b, void* out, float alpha, float beta, size_t n, int dtype, void* stream) {
     return axpby_launch(a, b, out, alpha, beta, nullptr, nullptr, n, dtype, stream);
@@ -644,24 +622,24 @@ __global__ __launch_bounds__(256) void blur3x3s_kernel(const T* __restrict__ x, 
 }
 // SGX_BLUR_SHFL: 0 = the three-load kernel everywhere, 1..4 = the one-load kernel at that prefetch depth; unset: the depth measured best
 // per mode (tools/blur_probe.py, profiles/r04_blur_probe.txt)
+SGX_SWITCH(blur_shfl_env, "SGX_BLUR_SHFL", -1)
 static int blur_shfl_pf(int mode) {
-    static const int env = [] { const char* e = getenv("SGX_BLUR_SHFL"); return e ? atoi(e) : -1; }();     // read once per process
-    if (env >= 0) return env;
+    if (blur_shfl_env() >= 0) return blur_shfl_env();
     return (mode == 1 || mode == 5) ? 1 : 3;                 // (the modes with a pre-op are the register-heavier ones: more waves beat a deeper ring)
 }
+// nontemporal accesses (bf16, the default prefetch depths): a PROBE (SGX_BLUR_NT=1), off by default.  Alone at batch 32
+// (tools/blur_rows_probe.py) they gain: 512^2 x 32 204.6 -> 194.8 us, 256^2 x 64 107.1 -> 98.9 (1024^2 x 16 406 -> 432: the strips' halo
+// rows are the neighbour block's L2 hits there) -- but INSIDE the step they lose: blur1 512^2 209.7 -> 230.1 us, blur0 204.4 -> 213.5,
+// 256^2 103 -> 110..113 (same box, single-stream layer tables): the blur's input was written by the launch before it and its output is
+// read by the launch after it, and a good part of a 268-537 MB tensor is still in the 256 MB memory-side cache unless the hint evicts it
+SGX_SWITCH(blur_nt, "SGX_BLUR_NT", 0)
 template <typename T, int PF, int ROWS = BLUR_ROWS>
 static void blur_launch_shfl(const void* x, const void* z, void* y, int B, int H, int W, int C, int mode, hipStream_t st) {
     constexpr int VE = VecTraits<T>::VE;
     const dim3 grid(grid_all((size_t)B * ((H + ROWS - 1) / ROWS) * W * C / VE)), block(256);
-    const T* xp = (const T*)x; const T* zp = (const T*)z; T* yp = (T*)y;
-    // nontemporal accesses (bf16, the default prefetch depths): a PROBE (SGX_BLUR_NT=1), off by default.  Alone at batch 32
-    // (tools/blur_rows_probe.py) they gain: 512^2 x 32 204.6 -> 194.8 us, 256^2 x 64 107.1 -> 98.9 (1024^2 x 16 406 -> 432: the strips' halo
-    // rows are the neighbour block's L2 hits there) -- but INSIDE the step they lose: blur1 512^2 209.7 -> 230.1 us, blur0 204.4 -> 213.5,
-    // 256^2 103 -> 110..113 (same box, single-stream layer tables): the blur's input was written by the launch before it and its output is
-    // read by the launch after it, and a good part of a 268-537 MB tensor is still in the 256 MB memory-side cache unless the hint evicts it
-    static const int blur_nt = [] { const char* e = getenv("SGX_BLUR_NT"); return e ? atoi(e) : 0; }();
+    const T* xp = as<T>(x); const T* zp = as<T>(z); T* yp = as<T>(y);
     if constexpr (sizeof(T) == 2 && (PF == 1 || PF == 3)) {
-        if (blur_nt && C >= 32 && sgx_nt_for((double)sizeof(T) * B * H * W * C)) {
+        if (blur_nt() && C >= 32 && sgx_nt_for((double)sizeof(T) * B * H * W * C)) {
             switch (mode) {
                 case 0: hipLaunchKernelGGL((blur3x3s_kernel<T, 0, ROWS, PF, true>), grid, block, 0, st, xp, zp, yp, B, H, W, C); break;
                 case 1: hipLaunchKernelGGL((blur3x3s_kernel<T, 1, ROWS, PF, true>), grid, block, 0, st, xp, zp, yp, B, H, W, C); break;
@@ -684,7 +662,7 @@ template <typename T, int ROWS>
 static void blur_launch_rows(const void* x, const void* z, void* y, int B, int H, int W, int C, int mode, hipStream_t st) {
     constexpr int VE = VecTraits<T>::VE;
     const dim3 grid(grid_all((size_t)B * ((H + ROWS - 1) / ROWS) * W * C / VE)), block(256);
-    const T* xp = (const T*)x; const T* zp = (const T*)z; T* yp = (T*)y;
+    const T* xp = as<T>(x); const T* zp = as<T>(z); T* yp = as<T>(y);
     switch (mode) {
         case 0: hipLaunchKernelGGL((blur3x3_kernel<T, 0, ROWS>), grid, block, 0, st, xp, zp, yp, B, H, W, C); break;
         case 1: hipLaunchKernelGGL((blur3x3_kernel<T, 1, ROWS>), grid, block, 0, st, xp, zp, yp, B, H, W, C); break;
@@ -714,12 +692,14 @@ static void blur_launch(const void* x, const void* z, void* y, int B, int H, int
 extern "C" int sgx_blur3x3_act(const void* x, const void* z, void* y, int B, int H, int W, int C, int mode, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(mode >= 0 && mode <= 3 && (mode < 2 || z), SGX_EINVAL, "blur3x3_act: mode %d", mode);
-    SGX_REQUIRE(dtype == SGX_F32 ? C % 4 == 0 : C % 8 == 0, SGX_EUNSUPPORTED, "blur: C=%d", C);
-    SGX_NOTE(0.0, (mode >= 2 ? 3.0 : 2.0) * (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * C, "blur%d B%d %dx%d C%d", mode, B, H, W, C);
-    if (dtype == SGX_F32) blur_launch<float>(x, z, y, B, H, W, C, mode, st);
-    else blur_launch<bf16_t>(x, z, y, B, H, W, C, mode, st);
-    SGX_LAUNCH_CHECK("blur3x3");
-    return 0;
+    return sgx_by_dtype(dtype, "blur3x3_act", [&](auto t) -> int {
+        using T = decltype(t);
+        SGX_REQUIRE(C % VecTraits<T>::VE == 0, SGX_EUNSUPPORTED, "blur: C=%d", C);
+        SGX_NOTE(0.0, (mode >= 2 ? 3.0 : 2.0) * sgx_esize(dtype) * B * H * W * C, "blur%d B%d %dx%d C%d", mode, B, H, W, C);
+        blur_launch<T>(x, z, y, B, H, W, C, mode, st);
+        SGX_LAUNCH_CHECK("blur3x3");
+        return 0;
+    });
 }
 extern "C" int sgx_blur3x3(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {
     return sgx_blur3x3_act(x, nullptr, y, B, H, W, C, 0, dtype, stream);
@@ -727,6 +707,7 @@ extern "C" int sgx_blur3x3(const void* x, void* y, int B, int H, int W, int C, i
 // modes 2 / 3 of sgx_blur3x3_act with the pre-activation given as sign bits ([pixel][C / 8] bytes, sgx_conv3x3_signbits); bf16
 extern "C" int sgx_blur3x3_bits(const void* x, const void* bits, void* y, int B, int H, int W, int C, int mode, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    SGX_REQUIRE(sgx_dtype_ok(dtype), SGX_EINVAL, "blur3x3_bits: dtype %d", dtype);
     SGX_REQUIRE((mode == 2 || mode == 3) && bits, SGX_EINVAL, "blur3x3_bits: mode %d", mode);
     SGX_REQUIRE(dtype == SGX_BF16 && C % 8 == 0, SGX_EUNSUPPORTED, "blur3x3_bits: bf16 with C %% 8 == 0 (C=%d dtype=%d)", C, dtype);
     SGX_NOTE(0.0, (2.0 * 2.0 + 1.0 / 8.0) * B * H * W * C, "blur%db B%d %dx%d C%d", mode, B, H, W, C);
@@ -780,16 +761,17 @@ extern "C" int sgx_blur_kxk(const void* x, void* y, const float* taps_host, int 
     SGX_REQUIRE(taps_host && K >= 1 && K <= SGX_BLUR_MAXK && pad >= 0 && pad < K, SGX_EINVAL, "blur_kxk: K=%d pad=%d (K <= %d)", K, pad, SGX_BLUR_MAXK);
     SGX_REQUIRE(OH >= 1 && OW >= 1 && OH <= IH + 2 * pad - K + 1 && OW <= IW + 2 * pad - K + 1, SGX_EINVAL,
                 "blur_kxk: output %dx%d does not fit input %dx%d with K=%d pad=%d", OH, OW, IH, IW, K, pad);
-    SGX_REQUIRE(dtype == SGX_F32 ? C % 4 == 0 : (dtype == SGX_BF16 && C % 8 == 0), SGX_EUNSUPPORTED, "blur_kxk: C=%d dtype=%d", C, dtype);
     BlurTaps t;
     for (int i = 0; i < K * K; ++i) t.k[i] = taps_host[i];
-    SGX_NOTE(0.0, (dtype == SGX_F32 ? 4.0 : 2.0) * B * C * ((double)IH * IW + (double)OH * OW), "blur_k%d B%d %dx%d C%d", K, B, IH, IW, C);
-    if (dtype == SGX_F32)
-        hipLaunchKernelGGL(blur_kxk_kernel<float>, dim3(grid_for((size_t)B * OH * OW * C / 4)), dim3(256), 0, st, (const float*)x, (float*)y, t, K, pad, B, IH, IW, OH, OW, C);
-    else
-        hipLaunchKernelGGL(blur_kxk_kernel<bf16_t>, dim3(grid_for((size_t)B * OH * OW * C / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, t, K, pad, B, IH, IW, OH, OW, C);
-    SGX_LAUNCH_CHECK("blur_kxk");
-    return 0;
+    return sgx_by_dtype(dtype, "blur_kxk", [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C % VE == 0, SGX_EUNSUPPORTED, "blur_kxk: C=%d dtype=%d", C, dtype);
+        SGX_NOTE(0.0, sgx_esize(dtype) * B * C * ((double)IH * IW + (double)OH * OW), "blur_k%d B%d %dx%d C%d", K, B, IH, IW, C);
+        hipLaunchKernelGGL(blur_kxk_kernel<T>, dim3(grid_for((size_t)B * OH * OW * C / VE)), dim3(256), 0, st, as<T>(x), as<T>(y), t, K, pad, B, IH, IW, OH, OW, C);
+        SGX_LAUNCH_CHECK("blur_kxk");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- 2x2 pooling / nearest upsample.  C generic (RGB has C=3):
@@ -852,20 +834,19 @@ __global__ __launch_bounds__(256) void pool2_rgb_kernel(const float* __restrict_
 }
 extern "C" int sgx_pool2(const void* x, void* y, int B, int H, int W, int C, float scale, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    SGX_NOTE(0.0, 1.25 * (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * C, "pool2 B%d %dx%d C%d", B, H, W, C);
+    SGX_NOTE(0.0, 1.25 * sgx_esize(dtype) * B * H * W * C, "pool2 B%d %dx%d C%d", B, H, W, C);
     SGX_REQUIRE(H % 2 == 0 && W % 2 == 0, SGX_EINVAL, "pool2: odd size");
     const size_t nout = (size_t)B * (H / 2) * (W / 2) * C;
-    if (dtype == SGX_F32) {
-        if (C % 4 == 0) hipLaunchKernelGGL((pool2_kernel<float, true>), dim3(grid_for(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
-        else if (C == 3 && W % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
+    return sgx_by_dtype(dtype, "pool2", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        if (C % VE == 0) hipLaunchKernelGGL((pool2_kernel<T, true>), dim3(grid_for(nout / VE)), dim3(256), 0, st, as<T>(x), as<T>(y), B, H, W, C, scale);
+        else if (sizeof(T) == 4 && C == 3 && W % 8 == 0 && sgx_aligned16(x) && sgx_aligned16(y))
             hipLaunchKernelGGL(pool2_rgb_kernel, dim3(grid_all(nout / 12)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
-        else hipLaunchKernelGGL((pool2_kernel<float, false>), dim3(grid_for(nout)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
-    } else {
-        if (C % 8 == 0) hipLaunchKernelGGL((pool2_kernel<bf16_t, true>), dim3(grid_for(nout / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C, scale);
-        else hipLaunchKernelGGL((pool2_kernel<bf16_t, false>), dim3(grid_for(nout)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C, scale);
-    }
-    SGX_LAUNCH_CHECK("pool2");
-    return 0;
+        else hipLaunchKernelGGL((pool2_kernel<T, false>), dim3(grid_for(nout)), dim3(256), 0, st, as<T>(x), as<T>(y), B, H, W, C, scale);
+        SGX_LAUNCH_CHECK("pool2");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- real images at the current depth with the fade-in blend
@@ -967,19 +948,16 @@ extern "C" int sgx_images_u8_to_nhwc(const void* src, void* dst, const int* flip
                                      void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(B > 0 && H > 0 && W > 0 && W % 4 == 0, SGX_EINVAL, "images_u8_to_nhwc: width must be a multiple of 4 (got %dx%d)", H, W);
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "images_u8_to_nhwc: bad dtype");
-    SGX_NOTE(0.0, (3.0 + 3.0 * (dtype == SGX_F32 ? 4.0 : 2.0)) * B * H * W, "images_u8 B%d %dx%d", B, H, W);
     const size_t n = (size_t)B * H * (W / 4);
     const auto* s = static_cast<const unsigned char*>(src);
-    if (dtype == SGX_F32) {
-        if (src_chw) hipLaunchKernelGGL((images_u8_kernel<float, true>), dim3(grid_for(n)), dim3(256), 0, st, s, (float*)dst, flip, B, H, W);
-        else hipLaunchKernelGGL((images_u8_kernel<float, false>), dim3(grid_for(n)), dim3(256), 0, st, s, (float*)dst, flip, B, H, W);
-    } else {
-        if (src_chw) hipLaunchKernelGGL((images_u8_kernel<bf16_t, true>), dim3(grid_for(n)), dim3(256), 0, st, s, (bf16_t*)dst, flip, B, H, W);
-        else hipLaunchKernelGGL((images_u8_kernel<bf16_t, false>), dim3(grid_for(n)), dim3(256), 0, st, s, (bf16_t*)dst, flip, B, H, W);
-    }
-    SGX_LAUNCH_CHECK("images_u8_kernel");
-    return 0;
+    return sgx_by_dtype(dtype, "images_u8_to_nhwc", [&](auto t) -> int {
+        using T = decltype(t);
+        SGX_NOTE(0.0, (3.0 + 3.0 * sgx_esize(dtype)) * B * H * W, "images_u8 B%d %dx%d", B, H, W);
+        if (src_chw) hipLaunchKernelGGL((images_u8_kernel<T, true>), dim3(grid_for(n)), dim3(256), 0, st, s, as<T>(dst), flip, B, H, W);
+        else hipLaunchKernelGGL((images_u8_kernel<T, false>), dim3(grid_for(n)), dim3(256), 0, st, s, as<T>(dst), flip, B, H, W);
+        SGX_LAUNCH_CHECK("images_u8_kernel");
+        return 0;
+    });
 }
 
 template <typename T, bool VECT>
@@ -1085,36 +1063,34 @@ __global__ void up2_add_kernel(const T* __restrict__ x, const T* __restrict__ a,
 extern "C" int sgx_up2_add(const void* x, const void* a, void* y, int B, int H, int W, int C, float scale, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(x && a && y && B > 0 && H > 0 && W > 0 && C > 0, SGX_EINVAL, "up2_add: bad arguments");
-    SGX_REQUIRE(dtype == SGX_F32 || dtype == SGX_BF16, SGX_EINVAL, "up2_add: bad dtype");
-    const double es = dtype == SGX_F32 ? 4.0 : 2.0;
-    SGX_NOTE(0.0, 9.0 * es * B * H * W * C, "up2+add B%d %dx%d C%d", B, H, W, C);
     const size_t nout = (size_t)B * H * W * 4 * C;
-    if (dtype == SGX_F32 && C == 3 && (2 * W * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
-        hipLaunchKernelGGL(up2_add_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (const float*)a, (float*)y, B, H, W, scale);
-    else if (dtype == SGX_F32)
-        hipLaunchKernelGGL(up2_add_kernel<float>, dim3(grid_for(nout)), dim3(256), 0, st, (const float*)x, (const float*)a, (float*)y, B, H, W, C, scale);
-    else
-        hipLaunchKernelGGL(up2_add_kernel<bf16_t>, dim3(grid_for(nout)), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)a, (bf16_t*)y, B, H, W, C, scale);
-    SGX_LAUNCH_CHECK("up2_add");
-    return 0;
+    return sgx_by_dtype(dtype, "up2_add", [&](auto t) -> int {
+        using T = decltype(t);
+        SGX_NOTE(0.0, 9.0 * sgx_esize(dtype) * B * H * W * C, "up2+add B%d %dx%d C%d", B, H, W, C);
+        if (sizeof(T) == 4 && C == 3 && (2 * W * 3) % 4 == 0 && sgx_aligned16(a) && sgx_aligned16(y))
+            hipLaunchKernelGGL(up2_add_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (const float*)a, (float*)y, B, H, W, scale);
+        else hipLaunchKernelGGL(up2_add_kernel<T>, dim3(grid_for(nout)), dim3(256), 0, st, as<T>(x), as<T>(a), as<T>(y), B, H, W, C, scale);
+        SGX_LAUNCH_CHECK("up2_add");
+        return 0;
+    });
 }
 extern "C" int sgx_up2(const void* x, void* y, int B, int H, int W, int C, float scale, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    SGX_NOTE(0.0, 5.0 * (dtype == SGX_F32 ? 4.0 : 2.0) * B * H * W * C, "up2 B%d %dx%d C%d", B, H, W, C);
+    SGX_NOTE(0.0, 5.0 * sgx_esize(dtype) * B * H * W * C, "up2 B%d %dx%d C%d", B, H, W, C);
     const size_t nout = (size_t)B * H * W * 4 * C;
-    if (dtype == SGX_F32) {
-        if (C % 4 == 0) hipLaunchKernelGGL((up2_kernel<float, true>), dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
-        else if (C == 3 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
+    return sgx_by_dtype(dtype, "up2", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        const bool rgb = sizeof(T) == 4 && C == 3;
+        if (C % VE == 0) hipLaunchKernelGGL((up2_kernel<T, true>), dim3(grid_all(nout / VE)), dim3(256), 0, st, as<T>(x), as<T>(y), B, H, W, C, scale);
+        else if (rgb && W % 4 == 0 && sgx_aligned16(x) && sgx_aligned16(y))
             hipLaunchKernelGGL(up2_rgb4_kernel, dim3(grid_all((size_t)B * H * (W / 4))), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
-        else if (C == 3 && (2 * W * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)           // (16-byte stores: y aligned; x is read by the float)
+        else if (rgb && (2 * W * 3) % 4 == 0 && sgx_aligned16(y))                                          // (16-byte stores: y aligned; x is read by the float)
             hipLaunchKernelGGL(up2_rgb_kernel, dim3(grid_all(nout / 4)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, scale);
-        else hipLaunchKernelGGL((up2_kernel<float, false>), dim3(grid_for(nout)), dim3(256), 0, st, (const float*)x, (float*)y, B, H, W, C, scale);
-    } else {
-        if (C % 8 == 0) hipLaunchKernelGGL((up2_kernel<bf16_t, true>), dim3(grid_all(nout / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C, scale);
-        else hipLaunchKernelGGL((up2_kernel<bf16_t, false>), dim3(grid_for(nout)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C, scale);
-    }
-    SGX_LAUNCH_CHECK("up2");
-    return 0;
+        else hipLaunchKernelGGL((up2_kernel<T, false>), dim3(grid_for(nout)), dim3(256), 0, st, as<T>(x), as<T>(y), B, H, W, C, scale);
+        SGX_LAUNCH_CHECK("up2");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- out[c] = sum_p x[p][c]
@@ -1219,26 +1195,29 @@ __global__ __launch_bounds__(256) void colsum_vec_stage1(const T* __restrict__ x
     }
 }
 static bool colsum_vec_ok(int C, int ve) { const int cv = C / ve; return C % ve == 0 && cv >= 1 && cv <= 256 && (cv & (cv - 1)) == 0; }
+static int colsum_blocks(size_t npix) {                     // stage-1 blocks of sgx_colsum and sgx_rgb_wgrad: 64 pixels each, at most COLSUM_BLOCKS
+    const size_t n = (npix + 63) / 64;
+    return n > COLSUM_BLOCKS ? COLSUM_BLOCKS : (n < 1 ? 1 : (int)n);
+}
 
 extern "C" size_t sgx_colsum_ws_bytes(size_t npix, int C) { (void)npix; return (size_t)COLSUM_BLOCKS * C * sizeof(double); }
 extern "C" int sgx_colsum(const void* x, float* out, float scale, void* ws, size_t ws_bytes, size_t npix, int C, int dtype, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(ws_bytes >= sgx_colsum_ws_bytes(npix, C), SGX_EWORKSPACE, "colsum: workspace");
     SGX_REQUIRE(C >= 1, SGX_EINVAL, "colsum: C=%d", C);     // scalar kernel: any C (C=3 for the RGB bias gradient)
-    SGX_NOTE(0.0, (dtype == SGX_F32 ? 4.0 : 2.0) * npix * C, "colsum %zux%d", npix, C);
-    int nblk = (int)((npix + 63) / 64);
-    if (nblk > COLSUM_BLOCKS) nblk = COLSUM_BLOCKS;
-    if (nblk < 1) nblk = 1;
-    if (dtype == SGX_F32 && colsum_vec_ok(C, 4))
-        hipLaunchKernelGGL((colsum_vec_stage1<float, 1>), dim3(nblk), dim3(256), 256 * 4 * sizeof(float), st, (const float*)x, (const float*)nullptr, (double*)ws, npix, C);
-    else if (dtype == SGX_BF16 && colsum_vec_ok(C, 8))
-        hipLaunchKernelGGL((colsum_vec_stage1<bf16_t, 1>), dim3(nblk), dim3(256), 256 * 8 * sizeof(float), st, (const bf16_t*)x, (const float*)nullptr, (double*)ws, npix, C);
-    else if (dtype == SGX_F32) hipLaunchKernelGGL(colsum_stage1<float>, dim3(nblk), dim3(256), 256 * sizeof(double), st, (const float*)x, (double*)ws, npix, C);
-    else hipLaunchKernelGGL(colsum_stage1<bf16_t>, dim3(nblk), dim3(256), 256 * sizeof(double), st, (const bf16_t*)x, (double*)ws, npix, C);
-    SGX_LAUNCH_CHECK("colsum_stage1");
-    hipLaunchKernelGGL(colsum_stage2, dim3((C + 3) / 4), dim3(256), 0, st, (const double*)ws, out, nblk, C, scale);
-    SGX_LAUNCH_CHECK("colsum_stage2");
-    return 0;
+    SGX_NOTE(0.0, sgx_esize(dtype) * npix * C, "colsum %zux%d", npix, C);
+    const int nblk = colsum_blocks(npix);
+    return sgx_by_dtype(dtype, "colsum", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        if (colsum_vec_ok(C, VE))
+            hipLaunchKernelGGL((colsum_vec_stage1<T, 1>), dim3(nblk), dim3(256), 256 * VE * sizeof(float), st, as<T>(x), (const float*)nullptr, (double*)ws, npix, C);
+        else hipLaunchKernelGGL(colsum_stage1<T>, dim3(nblk), dim3(256), 256 * sizeof(double), st, as<T>(x), (double*)ws, npix, C);
+        SGX_LAUNCH_CHECK("colsum_stage1");
+        hipLaunchKernelGGL(colsum_stage2, dim3((C + 3) / 4), dim3(256), 0, st, (const double*)ws, out, nblk, C, scale);
+        SGX_LAUNCH_CHECK("colsum_stage2");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- 1x1 RGB convolutions (3 <-> C), images fp32 [p][3]
@@ -1320,58 +1299,42 @@ __global__ __launch_bounds__(256) void rgb_in1_kernel(const float* __restrict__ 
         VecTraits<T>::store(y + (size_t)i * VE, v);
     }
 }
+SGX_SWITCH(rgb_in1_on, "SGX_RGB_IN1", 1)                   // A/B switch of rgb_in1_kernel
+// sgx_rgb_in (add NULL) and sgx_rgb_in_add (bias NULL): short-lived blocks for large launches, small ones keep the loop kernel.
+// Measured inside the single-stream step (same box, SGX_RGB_IN1=0 vs 1): batch 32 rgb_in 1024^2 x 16 288 -> 275 us, rgb_in+add 512^2 x 32 221 -> 188;
+// batch 4 52.5 -> 39.4 and 52.0 -> 30.0 us.  (Staging the block's pixels through LDS with 16-byte loads instead of three scalar loads per
+// vector: no better -- 285 / 189 and 43 / 33 us.)
 template <typename T>
-static bool rgb_in1_launch(const float* img, const float* w, int sj, int sc, float wscale, const float* bias, T* y, size_t npix, int C, const T* add, hipStream_t st) {
-    static const int on = [] { const char* e = getenv("SGX_RGB_IN1"); return e ? atoi(e) : 1; }();           // A/B switch
-    const size_t nvec = npix * (C / VecTraits<T>::VE);
-    // measured inside the single-stream step (same box, SGX_RGB_IN1=0 vs 1): batch 32 rgb_in 1024^2 x 16 288 -> 275 us, rgb_in+add 512^2 x 32 221 -> 188;
-    // batch 4 52.5 -> 39.4 and 52.0 -> 30.0 us.  (Staging the block's pixels through LDS with 16-byte loads instead of three scalar loads per
-    // vector: no better -- 285 / 189 and 43 / 33 us.)
-    if (!on || nvec < 65536 || nvec >= 0x7fffffffull || C > 2048) return false;                               // small launches keep the loop kernel
-    hipLaunchKernelGGL(rgb_in1_kernel<T>, dim3((unsigned)((nvec + 1023) / 1024)), dim3(256), (size_t)4 * C * sizeof(float), st, img, w, sj, sc, wscale, bias, y,
-                       (unsigned)nvec, C, add);
-    return true;
-}
-// the kernel hoists its channel group's weights, so the grid stride (256 * blocks) must be a multiple of cv
-static inline unsigned rgb_in_grid(size_t nvec, int cv) {
-    unsigned g = grid_for(nvec);
-    if (256 % cv != 0) g = (g + cv - 1) / cv * cv;
-    return g;
+static int rgb_in_run(const char* who, const float* img, const float* w, int sj, int sc, float wscale, const float* bias, const T* add, T* y, size_t npix, int C,
+                      hipStream_t st) {
+    constexpr int VE = VecTraits<T>::VE;
+    SGX_REQUIRE(C % VE == 0, SGX_EUNSUPPORTED, "%s: C %% %d", who, VE);
+    const size_t nvec = npix * (C / VE);
+    if (rgb_in1_on() && nvec >= 65536 && nvec < 0x7fffffffull && C <= 2048)
+        hipLaunchKernelGGL(rgb_in1_kernel<T>, dim3((unsigned)((nvec + 1023) / 1024)), dim3(256), (size_t)4 * C * sizeof(float), st, img, w, sj, sc, wscale, bias, y,
+                           (unsigned)nvec, C, add);
+    else hipLaunchKernelGGL(rgb_in_kernel<T>, dim3(grid_for_hoisted(nvec, C / VE)), dim3(256), 0, st, img, w, sj, sc, wscale, bias, y, npix, C, add);
+    SGX_LAUNCH_CHECK(who);
+    return 0;
 }
 extern "C" int sgx_rgb_in(const float* img, const float* w, int sj, int sc, float wscale, const float* bias, void* y, size_t npix, int C, int dtype, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    SGX_NOTE(6.0 * npix * C, npix * (12.0 + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "rgb_in %zux%d", npix, C);
-    if (dtype == SGX_F32) {
-        SGX_REQUIRE(C % 4 == 0, SGX_EUNSUPPORTED, "rgb_in: C %% 4");
-        if (!rgb_in1_launch<float>(img, w, sj, sc, wscale, bias, (float*)y, npix, C, (const float*)nullptr, st))
-        hipLaunchKernelGGL(rgb_in_kernel<float>, dim3(rgb_in_grid(npix * C / 4, C / 4)), dim3(256), 0, st, img, w, sj, sc, wscale, bias, (float*)y, npix, C, (const float*)nullptr);
-    } else {
-        SGX_REQUIRE(C % 8 == 0, SGX_EUNSUPPORTED, "rgb_in: C %% 8");
-        if (!rgb_in1_launch<bf16_t>(img, w, sj, sc, wscale, bias, (bf16_t*)y, npix, C, (const bf16_t*)nullptr, st))
-        hipLaunchKernelGGL(rgb_in_kernel<bf16_t>, dim3(rgb_in_grid(npix * C / 8, C / 8)), dim3(256), 0, st, img, w, sj, sc, wscale, bias, (bf16_t*)y, npix, C, (const bf16_t*)nullptr);
-    }
-    SGX_LAUNCH_CHECK("rgb_in");
-    return 0;
+    SGX_NOTE(6.0 * npix * C, npix * (12.0 + sgx_esize(dtype) * C), "rgb_in %zux%d", npix, C);
+    return sgx_by_dtype(dtype, "rgb_in", [&](auto t) -> int {
+        using T = decltype(t);
+        return rgb_in_run<T>("rgb_in", img, w, sj, sc, wscale, bias, nullptr, as<T>(y), npix, C, (hipStream_t)stream);
+    });
 }
 
 // y = add + sgx_rgb_in(img) (no bias): to_rgb's data gradient written ON TOP of the gradient the forked activation received from its other
 // consumer (generator under fade-in: a block's output feeds the next block and the previous resolution's to_rgb, models/GAN.py:199-202) --
 // one rounding and one pass instead of sgx_rgb_in + an add pass (read 2, write 1)
 extern "C" int sgx_rgb_in_add(const float* img, const float* w, int sj, int sc, float wscale, const void* add, void* y, size_t npix, int C, int dtype, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(img && w && add && y && npix > 0, SGX_EINVAL, "rgb_in_add: null argument");
-    SGX_NOTE(6.0 * npix * C, npix * (12.0 + 2.0 * (dtype == SGX_F32 ? 4.0 : 2.0) * C), "rgb_in+add %zux%d", npix, C);
-    if (dtype == SGX_F32) {
-        SGX_REQUIRE(C % 4 == 0, SGX_EUNSUPPORTED, "rgb_in_add: C %% 4");
-        if (!rgb_in1_launch<float>(img, w, sj, sc, wscale, (const float*)nullptr, (float*)y, npix, C, (const float*)add, st))
-        hipLaunchKernelGGL(rgb_in_kernel<float>, dim3(rgb_in_grid(npix * C / 4, C / 4)), dim3(256), 0, st, img, w, sj, sc, wscale, (const float*)nullptr, (float*)y, npix, C, (const float*)add);
-    } else {
-        SGX_REQUIRE(dtype == SGX_BF16 && C % 8 == 0, SGX_EUNSUPPORTED, "rgb_in_add: bf16 with C %% 8");
-        if (!rgb_in1_launch<bf16_t>(img, w, sj, sc, wscale, (const float*)nullptr, (bf16_t*)y, npix, C, (const bf16_t*)add, st))
-        hipLaunchKernelGGL(rgb_in_kernel<bf16_t>, dim3(rgb_in_grid(npix * C / 8, C / 8)), dim3(256), 0, st, img, w, sj, sc, wscale, (const float*)nullptr, (bf16_t*)y, npix, C, (const bf16_t*)add);
-    }
-    SGX_LAUNCH_CHECK("rgb_in_add");
-    return 0;
+    SGX_NOTE(6.0 * npix * C, npix * (12.0 + 2.0 * sgx_esize(dtype) * C), "rgb_in+add %zux%d", npix, C);
+    return sgx_by_dtype(dtype, "rgb_in_add", [&](auto t) -> int {
+        using T = decltype(t);
+        return rgb_in_run<T>("rgb_in_add", img, w, sj, sc, wscale, nullptr, as<T>(add), as<T>(y), npix, C, (hipStream_t)stream);
+    });
 }
 
 // one pixel per group of LPP lanes (LPP = C/VE capped at 16); partial dot products reduced with shuffles.
@@ -1497,39 +1460,37 @@ __global__ __launch_bounds__(256) void rgb_out1_kernel(const T* __restrict__ x, 
         }
     }
 }
+SGX_SWITCH(rgb_out1_on, "SGX_RGB_OUT1", 1)                 // A/B switch of rgb_out1_kernel
 static int rgb_out_launch(const void* x, const float* w, int sj, int sc, float wscale, const float* bias, float* img, size_t npix, int C, int dtype,
                           const float* low, int H, int W, float alpha, float beta, const float* ab_dev, hipStream_t st) {
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE(C % ve == 0 && C <= 4096, SGX_EUNSUPPORTED, "rgb_out: C=%d", C);
-    int lpp = C / ve;
-    if (lpp > 16) lpp = 16;
-    SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "rgb_out: C=%d", C);
-    const size_t sh = (size_t)3 * C * sizeof(float);
-    {   // short-lived blocks where every lane of a pixel group holds exactly one vector (C / ve == lpp <= 16) and the launch is large enough
-        static const int on = [] { const char* e = getenv("SGX_RGB_OUT1"); return e ? atoi(e) : 1; }();          // A/B switch
-        if (on && C / ve == lpp && npix >= 65536 && npix < 0x7fffffffull) {
+    return sgx_by_dtype(dtype, "rgb_out", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C % VE == 0 && C <= 4096, SGX_EUNSUPPORTED, "rgb_out: C=%d", C);
+        const int lpp = C / VE > 16 ? 16 : C / VE;
+        SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "rgb_out: C=%d", C);
+        const size_t sh = (size_t)3 * C * sizeof(float);
+        // short-lived blocks where every lane of a pixel group holds exactly one vector (C / VE == lpp <= 16) and the launch is large enough
+        if (rgb_out1_on() && C / VE == lpp && npix >= 65536 && npix < 0x7fffffffull) {
             const unsigned ppb4 = (unsigned)(256 / lpp) * 4, g1 = (unsigned)((npix + ppb4 - 1) / ppb4);
-            if (dtype == SGX_F32) hipLaunchKernelGGL(rgb_out1_kernel<float>, dim3(g1), dim3(256), sh, st, (const float*)x, w, sj, sc, wscale, bias, img, (unsigned)npix, C, lpp, low, H, W, alpha, beta, ab_dev);
-            else hipLaunchKernelGGL(rgb_out1_kernel<bf16_t>, dim3(g1), dim3(256), sh, st, (const bf16_t*)x, w, sj, sc, wscale, bias, img, (unsigned)npix, C, lpp, low, H, W, alpha, beta, ab_dev);
+            hipLaunchKernelGGL(rgb_out1_kernel<T>, dim3(g1), dim3(256), sh, st, as<T>(x), w, sj, sc, wscale, bias, img, (unsigned)npix, C, lpp, low, H, W, alpha, beta, ab_dev);
             SGX_LAUNCH_CHECK("rgb_out1");
             return 0;
         }
-    }
-    const unsigned g = grid_for(npix * lpp);
-    if (dtype == SGX_F32) hipLaunchKernelGGL(rgb_out_kernel<float>, dim3(g), dim3(256), sh, st, (const float*)x, w, sj, sc, wscale, bias, img, npix, C, lpp, low, H, W, alpha, beta, ab_dev);
-    else hipLaunchKernelGGL(rgb_out_kernel<bf16_t>, dim3(g), dim3(256), sh, st, (const bf16_t*)x, w, sj, sc, wscale, bias, img, npix, C, lpp, low, H, W, alpha, beta, ab_dev);
-    SGX_LAUNCH_CHECK("rgb_out");
-    return 0;
+        hipLaunchKernelGGL(rgb_out_kernel<T>, dim3(grid_for(npix * lpp)), dim3(256), sh, st, as<T>(x), w, sj, sc, wscale, bias, img, npix, C, lpp, low, H, W, alpha, beta, ab_dev);
+        SGX_LAUNCH_CHECK("rgb_out");
+        return 0;
+    });
 }
 extern "C" int sgx_rgb_out(const void* x, const float* w, int sj, int sc, float wscale, const float* bias, float* img, size_t npix, int C, int dtype, void* stream) {
-    SGX_NOTE(6.0 * npix * C, npix * (12.0 + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "rgb_out %zux%d", npix, C);
+    SGX_NOTE(6.0 * npix * C, npix * (12.0 + sgx_esize(dtype) * C), "rgb_out %zux%d", npix, C);
     return rgb_out_launch(x, w, sj, sc, wscale, bias, img, npix, C, dtype, nullptr, 1, 1, 1.f, 0.f, nullptr, (hipStream_t)stream);
 }
 extern "C" int sgx_rgb_out_fade(const void* x, const float* w, int sj, int sc, float wscale, const float* bias, const float* low, float alpha,
                                 float beta, const float* ab_dev, float* img, int B, int H, int W, int C, int dtype, void* stream) {
     SGX_REQUIRE(x && w && low && img && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, SGX_EINVAL, "rgb_out_fade: bad arguments (%dx%d)", H, W);
     const size_t npix = (size_t)B * H * W;
-    SGX_NOTE(6.0 * npix * C, npix * (12.0 + 3.0 + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "rgb_out+fade %zux%d", npix, C);
+    SGX_NOTE(6.0 * npix * C, npix * (12.0 + 3.0 + sgx_esize(dtype) * C), "rgb_out+fade %zux%d", npix, C);
     return rgb_out_launch(x, w, sj, sc, wscale, bias, img, npix, C, dtype, low, H, W, alpha, beta, ab_dev, (hipStream_t)stream);
 }
 
@@ -1611,27 +1572,24 @@ extern "C" int sgx_rgb_out_epi(const void* y, const float* ebias, const float* n
                                float beta, const float* ab_dev, float* img, int B, int H, int W, int C, int dtype, void* stream) {
     SGX_REQUIRE(y && noise && nw && mean && rstd && w && img && B > 0 && H > 0 && W > 0, SGX_EINVAL, "rgb_out_epi: bad arguments");
     SGX_REQUIRE(!low || (H % 2 == 0 && W % 2 == 0), SGX_EINVAL, "rgb_out_epi: odd size %dx%d with a low-resolution image", H, W);
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE((dtype == SGX_F32 || dtype == SGX_BF16) && C % ve == 0 && C <= 2048, SGX_EUNSUPPORTED, "rgb_out_epi: C=%d", C);
-    int lpp = C / ve;
-    if (lpp > 16) lpp = 16;
-    SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "rgb_out_epi: C=%d", C);
-    const int HW = H * W;
-    const double npix = (double)B * HW;
-    SGX_NOTE(8.0 * npix * C, npix * (12.0 + 4.0 + (low ? 3.0 : 0.0) + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "epi+rgb_out%s %.0fx%d", low ? "+fade" : "", npix, C);
-    long bx = ((long)HW * lpp + 255) / 256;
-    const long cap = 4096 / B > 1 ? 4096 / B : 1;
-    if (bx > cap) bx = cap;
-    const size_t sh = (size_t)(5 * C + 4 + 256 * 3) * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SGX_F32)
-        hipLaunchKernelGGL(rgb_out_epi_kernel<float>, dim3((unsigned)bx, (unsigned)B), dim3(256), sh, st, (const float*)y, ebias, noise, nw, style, mean, rstd, w, sj, sc,
+    return sgx_by_dtype(dtype, "rgb_out_epi", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(C % VE == 0 && C <= 2048, SGX_EUNSUPPORTED, "rgb_out_epi: C=%d", C);
+        const int lpp = C / VE > 16 ? 16 : C / VE;
+        SGX_REQUIRE((lpp & (lpp - 1)) == 0, SGX_EUNSUPPORTED, "rgb_out_epi: C=%d", C);
+        const int HW = H * W;
+        const double npix = (double)B * HW;
+        SGX_NOTE(8.0 * npix * C, npix * (12.0 + 4.0 + (low ? 3.0 : 0.0) + sgx_esize(dtype) * C), "epi+rgb_out%s %.0fx%d", low ? "+fade" : "", npix, C);
+        long bx = ((long)HW * lpp + 255) / 256;
+        const long cap = 4096 / B > 1 ? 4096 / B : 1;
+        if (bx > cap) bx = cap;
+        const size_t sh = (size_t)(5 * C + 4 + 256 * 3) * sizeof(float);
+        hipLaunchKernelGGL(rgb_out_epi_kernel<T>, dim3((unsigned)bx, (unsigned)B), dim3(256), sh, (hipStream_t)stream, as<T>(y), ebias, noise, nw, style, mean, rstd, w, sj, sc,
                            wscale, rbias, img, HW, C, lpp, low, H, W, alpha, beta, ab_dev);
-    else
-        hipLaunchKernelGGL(rgb_out_epi_kernel<bf16_t>, dim3((unsigned)bx, (unsigned)B), dim3(256), sh, st, (const bf16_t*)y, ebias, noise, nw, style, mean, rstd, w, sj,
-                           sc, wscale, rbias, img, HW, C, lpp, low, H, W, alpha, beta, ab_dev);
-    SGX_LAUNCH_CHECK("rgb_out_epi");
-    return 0;
+        SGX_LAUNCH_CHECK("rgb_out_epi");
+        return 0;
+    });
 }
 
 // to_rgb's weight and bias gradient with the epilogue recomputed from y:  dW[j][c] = scale sum_b (A[b][c] G1[b][j][c] + S[b][c] G0[b][j]),
@@ -1731,18 +1689,20 @@ extern "C" int sgx_rgb_wgrad_epi(const void* y, const float* g, const float* ebi
                                  int C, int dtype, void* stream) {
     SGX_REQUIRE(y && g && noise && nw && mean && rstd && dw && ws, SGX_EINVAL, "rgb_wgrad_epi: null argument");
     SGX_REQUIRE(ws_bytes >= sgx_rgb_wgrad_epi_ws_bytes(B, HW, C), SGX_EWORKSPACE, "rgb_wgrad_epi: workspace");
-    const int ve = dtype == SGX_F32 ? 4 : 8;
-    SGX_REQUIRE((dtype == SGX_F32 || dtype == SGX_BF16) && colsum_vec_ok(C, ve), SGX_EUNSUPPORTED, "rgb_wgrad_epi: C=%d", C);
-    const int nblk = rgb_wgrad_epi_blocks(B, HW);
-    SGX_NOTE(8.0 * (double)B * HW * C, (double)B * HW * (12.0 + 4.0 + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "epi+rgb_wgrad %dx%d", B * HW, C);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t sh = (size_t)256 * (3 * ve + 3) * sizeof(float);
-    if (dtype == SGX_F32) hipLaunchKernelGGL(rgb_wgrad_epi_stage1<float>, dim3(nblk, B), dim3(256), sh, st, (const float*)y, g, ebias, noise, nw, (double*)ws, HW, C);
-    else hipLaunchKernelGGL(rgb_wgrad_epi_stage1<bf16_t>, dim3(nblk, B), dim3(256), sh, st, (const bf16_t*)y, g, ebias, noise, nw, (double*)ws, HW, C);
-    SGX_LAUNCH_CHECK("rgb_wgrad_epi_stage1");
-    hipLaunchKernelGGL(rgb_wgrad_epi_stage2, dim3(3 * C + 3), dim3(256), 0, st, (const double*)ws, style, mean, rstd, dw, db, B, nblk, C, sj, sc, scale, bscale);
-    SGX_LAUNCH_CHECK("rgb_wgrad_epi_stage2");
-    return 0;
+    return sgx_by_dtype(dtype, "rgb_wgrad_epi", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        SGX_REQUIRE(colsum_vec_ok(C, VE), SGX_EUNSUPPORTED, "rgb_wgrad_epi: C=%d", C);
+        const int nblk = rgb_wgrad_epi_blocks(B, HW);
+        SGX_NOTE(8.0 * (double)B * HW * C, (double)B * HW * (12.0 + 4.0 + sgx_esize(dtype) * C), "epi+rgb_wgrad %dx%d", B * HW, C);
+        hipStream_t st = (hipStream_t)stream;
+        const size_t sh = (size_t)256 * (3 * VE + 3) * sizeof(float);
+        hipLaunchKernelGGL(rgb_wgrad_epi_stage1<T>, dim3(nblk, B), dim3(256), sh, st, as<T>(y), g, ebias, noise, nw, (double*)ws, HW, C);
+        SGX_LAUNCH_CHECK("rgb_wgrad_epi_stage1");
+        hipLaunchKernelGGL(rgb_wgrad_epi_stage2, dim3(3 * C + 3), dim3(256), 0, st, (const double*)ws, style, mean, rstd, dw, db, B, nblk, C, sj, sc, scale, bscale);
+        SGX_LAUNCH_CHECK("rgb_wgrad_epi_stage2");
+        return 0;
+    });
 }
 
 // dw[j][c] = sum_p img[p][j] * f[p][c]: stage 1 partials per block in double, stage 2 sums them.
@@ -1798,18 +1758,17 @@ extern "C" int sgx_rgb_wgrad(const float* img, const void* f, float* dw, int sj,
     hipStream_t st = (hipStream_t)stream;
     SGX_REQUIRE(ws_bytes >= sgx_rgb_wgrad_ws_bytes(npix, C), SGX_EWORKSPACE, "rgb_wgrad: workspace");
     SGX_REQUIRE(C <= 256 ? (256 % C == 0) : true, SGX_EUNSUPPORTED, "rgb_wgrad: C=%d", C);
-    SGX_NOTE(6.0 * npix * C, npix * (12.0 + (dtype == SGX_F32 ? 4.0 : 2.0) * C), "rgb_wgrad %zux%d", npix, C);
-    int nblk = (int)((npix + 63) / 64);
-    if (nblk > COLSUM_BLOCKS) nblk = COLSUM_BLOCKS;
-    if (nblk < 1) nblk = 1;
-    if (dtype == SGX_F32 && colsum_vec_ok(C, 4))
-        hipLaunchKernelGGL((colsum_vec_stage1<float, 3>), dim3(nblk), dim3(256), 256 * 12 * sizeof(float), st, (const float*)f, img, (double*)ws, npix, C);
-    else if (dtype == SGX_BF16 && colsum_vec_ok(C, 8))
-        hipLaunchKernelGGL((colsum_vec_stage1<bf16_t, 3>), dim3(nblk), dim3(256), 256 * 24 * sizeof(float), st, (const bf16_t*)f, img, (double*)ws, npix, C);
-    else if (dtype == SGX_F32) hipLaunchKernelGGL(rgb_wgrad_stage1<float>, dim3(nblk), dim3(256), 768 * sizeof(double), st, img, (const float*)f, (double*)ws, npix, C);
-    else hipLaunchKernelGGL(rgb_wgrad_stage1<bf16_t>, dim3(nblk), dim3(256), 768 * sizeof(double), st, img, (const bf16_t*)f, (double*)ws, npix, C);
-    SGX_LAUNCH_CHECK("rgb_wgrad_stage1");
-    hipLaunchKernelGGL(rgb_wgrad_stage2, dim3((3 * C + 3) / 4), dim3(256), 0, st, (const double*)ws, dw, nblk, C, sj, sc, wscale);
-    SGX_LAUNCH_CHECK("rgb_wgrad_stage2");
-    return 0;
+    SGX_NOTE(6.0 * npix * C, npix * (12.0 + sgx_esize(dtype) * C), "rgb_wgrad %zux%d", npix, C);
+    const int nblk = colsum_blocks(npix);
+    return sgx_by_dtype(dtype, "rgb_wgrad", [&](auto t) -> int {
+        using T = decltype(t);
+        constexpr int VE = VecTraits<T>::VE;
+        if (colsum_vec_ok(C, VE))
+            hipLaunchKernelGGL((colsum_vec_stage1<T, 3>), dim3(nblk), dim3(256), 256 * 3 * VE * sizeof(float), st, as<T>(f), img, (double*)ws, npix, C);
+        else hipLaunchKernelGGL(rgb_wgrad_stage1<T>, dim3(nblk), dim3(256), 768 * sizeof(double), st, img, as<T>(f), (double*)ws, npix, C);
+        SGX_LAUNCH_CHECK("rgb_wgrad_stage1");
+        hipLaunchKernelGGL(rgb_wgrad_stage2, dim3((3 * C + 3) / 4), dim3(256), 0, st, (const double*)ws, dw, nblk, C, sj, sc, wscale);
+        SGX_LAUNCH_CHECK("rgb_wgrad_stage2");
+        return 0;
+    });
 }

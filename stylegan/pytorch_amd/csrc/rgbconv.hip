@@ -725,9 +725,9 @@ __global__ __launch_bounds__(256) void rgbconv_chain_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
+SGX_SWITCH(rgbconv_on, "SGX_RGBCONV", 1)                   // A/B switch
 static bool rgbconv_shape_ok(int B, int H, int W, int C, int dtype) {
-    static const int on = [] { const char* e = getenv("SGX_RGBCONV"); return e ? atoi(e) : 1; }();     // A/B switch
-    return on && dtype == SGX_BF16 && (C == 16 || C == 32) && B >= 1 && H >= 16 && W >= 64 && H % 16 == 0 && W % 64 == 0;
+    return rgbconv_on() && dtype == SGX_BF16 && (C == 16 || C == 32) && B >= 1 && H >= 16 && W >= 64 && H % 16 == 0 && W % 64 == 0;
 }
 extern "C" int sgx_rgbconv_ok(int B, int H, int W, int C, int dtype) { return rgbconv_shape_ok(B, H, W, C, dtype) ? 1 : 0; }
 

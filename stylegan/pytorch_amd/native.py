@@ -48,6 +48,7 @@ SIGNATURES = {
     "sgx_prof_start": (I, [I, I]),
     "sgx_prof_count": (I, []),
     "sgx_prof_get": (I, [I, P, I, P, P, P, P, I]),
+    "sgx_prof_get_launch": (I, [I, P, P, P]),
     "sgx_pack_weight": (I, [P, P, P, I, I, I, I, F, I, P]),
     "sgx_pack_weight_multi": (I, [P, I, I, I, P]),
     "sgx_pack_weight_blocks": (I, [I, I]),
@@ -387,4 +388,15 @@ def prof_records():
         check(L.sgx_prof_get(i, ctypes.addressof(name), 256, ctypes.addressof(ms), ctypes.addressof(fl), ctypes.addressof(by),
                              ctypes.addressof(desc), 64), "sgx_prof_get")
         out.append((name.value.decode(), ms.value, fl.value, by.value, desc.value.decode()))
+    return out
+
+
+def prof_launches():
+    """[((grid x, y, z), (block x, y, z), dynamic LDS bytes), ...]: the launch geometry of every record of prof_records(), in the same order."""
+    L = lib()
+    grid, block, lds = (ctypes.c_uint * 3)(), (ctypes.c_uint * 3)(), ctypes.c_size_t()
+    out = []
+    for i in range(L.sgx_prof_count()):
+        check(L.sgx_prof_get_launch(i, ctypes.addressof(grid), ctypes.addressof(block), ctypes.addressof(lds)), "sgx_prof_get_launch")
+        out.append((tuple(grid), tuple(block), lds.value))
     return out

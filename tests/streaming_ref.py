@@ -9,7 +9,9 @@ on the absolute values of inputs and coefficients.  ``S`` is the per-element sca
 expression in fp32 with a longest chain of ``n`` operations is within ``n * 2^-24 * S`` of ``ref`` to first order (each rounding is
 relative to a partial result that is bounded by the same partial expression on absolute values).  Coefficients are given as the fp32
 values the C ABI receives (``f32()``)."""
+import json
 import math
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -308,6 +310,34 @@ def tname(dtype):
     return "float" if dtype == torch.float32 else "bf16_t"
 
 
+# ---------------------------------------------------------------------------------------------------------------- launch geometry
+# tests/golden/streaming_launch.json: {row id: [[kernel id, grid x, y, z, block x, y, z, dynamic LDS bytes], ...]}, every launch a row makes
+# through a launch() helper of the GPU tests, in order, as tests/streaming_runner.py --write-geometry recorded it.  None of these launchers
+# sizes a grid from the device, so a row is a function of its arguments and the environment.
+GEOMETRY_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "streaming_launch.json")
+RECORDER = None                     # tests/streaming_runner.py: a function (row id, launches) that takes the launches in place of the comparison
+_geometry, _cursor = None, {}
+
+
+def check_geometry(row, kernels, launches):
+    """One profiled call of a row: kernel_id() of its launches and native.prof_launches() of the same records against the fixture.  A row's
+    calls follow each other in the fixture (the cursor starts over when a row is run again); a row id the fixture does not have fails."""
+    global _geometry
+    got = [[k, *g, *b, int(lds)] for k, (g, b, lds) in zip(kernels, launches)]
+    assert len(got) == len(kernels) == len(launches), (row, kernels, launches)
+    if RECORDER is not None:
+        return RECORDER(row, got)
+    if _geometry is None:
+        with open(GEOMETRY_PATH) as f:
+            _geometry = json.load(f)
+    assert row in _geometry, f"{row}: no row in tests/golden/streaming_launch.json"
+    want = _geometry[row]
+    at = _cursor.get(row, 0)
+    at = 0 if at >= len(want) else at
+    assert got == want[at:at + len(got)], f"{row}: launched {got}, recorded {want[at:at + len(got)]} (launches {at}.. of the row)"
+    _cursor[row] = at + len(got)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the case table
 # entry: the C ABI function; dtype: of the activations; args: what the runner of that entry in tests/test_gpu_streaming_kernels.py reads;
 # kernels: kernel_id() of every launch the call is expected to make, in order; why: the launcher rule that selects them for this shape.
@@ -536,7 +566,8 @@ REJECTIONS = [
     ("colsum-short-workspace", "sgx_colsum", -3, "workspace one byte short"),
     ("rgb_wgrad-C48", "sgx_rgb_wgrad", -2, "C <= 256 that does not divide 256"),
     ("rgb_out-C4104", "sgx_rgb_out", -2, "C above 4096"),
-]
+] + [(f"{e[4:]}-dtype7", e, -1, "a dtype outside {SGX_F32, SGX_BF16}: the one dtype dispatch refuses it")
+     for e in ("sgx_bias_act", "sgx_pool2", "sgx_up2", "sgx_up2_add", "sgx_colsum", "sgx_rgb_in", "sgx_rgb_out", "sgx_lrelu_bwd_bits", "sgx_img_in")]
 
 # Launch sites of the covered sources that no case reaches, each with its reason (tests/test_streaming_coverage.py).  Keys are the kernel
 # expressions as the hipLaunchKernelGGL sites spell them.

@@ -45,7 +45,8 @@ def d(t):
 
 
 def launch(what, call, kernels):
-    """One C ABI call under the library's profiler: it succeeds and launches exactly ``kernels``, in order."""
+    """One C ABI call under the library's profiler: it succeeds and launches exactly ``kernels``, in order, each with the grid, block and
+    dynamic LDS size of tests/golden/streaming_launch.json (``what`` is the row id)."""
     N = _native()
     N.prof_start(1)
     try:
@@ -56,6 +57,7 @@ def launch(what, call, kernels):
     N.check(rc, what)
     ran = [SR.kernel_id(r[0]) for r in N.prof_records()]
     assert ran == list(kernels), f"{what}: launched {ran}, expected {list(kernels)}"
+    SR.check_geometry(what, ran, N.prof_launches())
 
 
 def check(g, ref, S, n, what):

@@ -1,6 +1,7 @@
 """-m gpu: every HIP kernel of libsgx_hip.so, called through the module / autograd surface, against the CPU oracle
 (fp64) on the same seeded inputs.  fp32 bar: rel-L2 <= 1e-3 per tensor (BASELINE north_star); observed ~1e-6."""
 import math
+import os
 
 import pytest
 import torch
@@ -579,40 +580,62 @@ def test_act_blur_first_and_second_order(dt):
     assert_close(dg, dgr, tol, "act_blur double backward")
 
 
-# (tensors large enough for the streaming blur kernels: 8-row strips, >= 131072 strip lanes; heights that are not strip multiples)
-@pytest.mark.parametrize("dt,B,H,W,C", [(torch.bfloat16, 6, 200, 512, 16), (torch.bfloat16, 10, 52, 256, 64), (torch.bfloat16, 16, 36, 128, 128),
-                                        (torch.bfloat16, 3, 99, 448, 32), (torch.float32, 16, 72, 256, 16)])
-def test_one_load_blur_kernel_writes_the_bits_of_the_three_load_kernel(dt, B, H, W, C, monkeypatch):
+_BLUR_CHILDREN = {}                 # SGX_BLUR_SHFL value -> {(shape index, mode): (kernel id, sha256)}, or "error" -> what stopped the children
+
+
+def blur_children():
+    """tests/blur_bits_child.py once per SGX_BLUR_SHFL value, each in a fresh process (the library reads the variable once per process), one
+    after the other.  A child that fails, reports a HIP error or runs out of time ends it: nothing more is started, by later cases either."""
+    import json
+    import subprocess
+    import sys
+    import blur_bits_child as BC
+    if not _BLUR_CHILDREN:
+        for v in ("0", "2"):
+            try:
+                r = subprocess.run([sys.executable, BC.__file__], env=dict(os.environ, SGX_BLUR_SHFL=v), capture_output=True, text=True, timeout=180)
+            except subprocess.TimeoutExpired:
+                _BLUR_CHILDREN["error"] = f"SGX_BLUR_SHFL={v}: the child ran out of time"
+                break
+            rows = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+            if r.returncode != 0 or any("error" in row for row in rows):
+                _BLUR_CHILDREN["error"] = f"SGX_BLUR_SHFL={v}: exit {r.returncode}: {r.stdout[-600:]} {r.stderr[-600:]}"
+                break
+            _BLUR_CHILDREN[v] = {(row["shape"], row["mode"]): (row["kernel"], row["sha256"]) for row in rows}
+    assert "error" not in _BLUR_CHILDREN, _BLUR_CHILDREN["error"]
+    return _BLUR_CHILDREN
+
+
+def _blur_shapes():
+    import blur_bits_child as BC
+    return BC.SHAPES
+
+
+@pytest.mark.parametrize("dt,B,H,W,C", _blur_shapes())
+def test_one_load_blur_kernel_writes_the_bits_of_the_three_load_kernel(dt, B, H, W, C):
     """csrc/pointwise.hip blur3x3s_kernel (round 4: one global load per input vector, neighbours by lane exchange, pre-op once per
-    element) against blur3x3_kernel (SGX_BLUR_SHFL=0, read at every launch): every mode, bit for bit -- and mode 0 / 1 against torch
-    (reference models/CustomLayers.py:179-217: the depthwise [1,2,1]x[1,2,1]/16 blur with zero padding)."""
-    from stylegan.pytorch_amd import native as N
-    L = N.lib()
-    torch.manual_seed(C + H)
-    x = torch.randn(B, H, W, C, device=DEV).to(dt)
-    z = torch.randn(B, H, W, C, device=DEV).to(dt)
-    bits = torch.randint(0, 256, (B, H, W, C // 8), device=DEV, dtype=torch.uint8)
-    iview = torch.int16 if dt == torch.bfloat16 else torch.int32
+    element) against blur3x3_kernel: every mode, bit for bit -- and mode 0 / 1 against torch (reference models/CustomLayers.py:179-217:
+    the depthwise [1,2,1]x[1,2,1]/16 blur with zero padding).  SGX_BLUR_SHFL is read once per process, so the three-load kernel
+    (SGX_BLUR_SHFL=0) and the one-load kernel at depth 2 (=2) each run in a fresh child process, this process runs the default depth, and the
+    profiler's kernel names say that each arm ran what it stands for."""
+    import re
+    import blur_bits_child as BC
+    si = BC.SHAPES.index((dt, B, H, W, C))
+    kids = blur_children()
+    x, mine = BC.run(dt, B, H, W, C)
     k = torch.tensor([1., 2., 1.], device=DEV); k = (k[:, None] * k[None, :] / 16.0)[None, None].repeat(C, 1, 1, 1)
-    for mode in ([0, 1, 2, 4, 5] if dt == torch.bfloat16 else [0, 1, 2]):
-        outs = []
-        for v in ("0", None, "2"):
-            if v is None:
-                monkeypatch.delenv("SGX_BLUR_SHFL", raising=False)
-            else:
-                monkeypatch.setenv("SGX_BLUR_SHFL", v)
-            y = torch.full_like(x, 7.0)
-            if mode >= 4:
-                N.check(L.sgx_blur3x3_bits(N.ptr(x), N.ptr(bits), N.ptr(y), B, H, W, C, mode - 2, N.dt(x), N.stream()), "blur_bits")
-            else:
-                N.check(L.sgx_blur3x3_act(N.ptr(x), N.ptr(z if mode == 2 else None), N.ptr(y), B, H, W, C, mode, N.dt(x), N.stream()), "blur_act")
-            outs.append(y)
-        assert torch.equal(outs[0].view(iview), outs[1].view(iview)), (mode, "default depth")
-        assert torch.equal(outs[0].view(iview), outs[2].view(iview)), (mode, "depth 2")
+    for mode in BC.modes(dt):
+        y, kernel, sha = mine[mode]
+        (k0, sha0), (k2, sha2) = kids["0"][(si, mode)], kids["2"][(si, mode)]
+        assert re.match(rf"blur3x3_kernel<\w+, {mode}, \d+>$", k0), (mode, k0)
+        assert re.match(rf"blur3x3s_kernel<\w+, {mode}, \d+, 2, (true|false)>$", k2), (mode, k2)
+        assert re.match(rf"blur3x3s_kernel<\w+, {mode}, \d+, [13], (true|false)>$", kernel), (mode, kernel)
+        assert sha0 == sha, (mode, "default depth")
+        assert sha0 == sha2, (mode, "depth 2")
         if mode in (0, 1):
             a = x.float().permute(0, 3, 1, 2)
             ref = TF.conv2d(TF.leaky_relu(a, 0.2) if mode == 1 else a, k, padding=1, groups=C).permute(0, 2, 3, 1)
-            assert_close(outs[1], ref, 1e-5 if dt == torch.float32 else 8e-3, f"blur mode {mode}")
+            assert_close(y, ref, 1e-5 if dt == torch.float32 else 8e-3, f"blur mode {mode}")
 
 
 @pytest.mark.parametrize("act", [0, 1])

@@ -84,7 +84,8 @@ _FAULT = None
 
 
 def launch(c, call, kernels=None):
-    """Run one C ABI call under the library's profiler: it succeeds and launches exactly the expected kernels, in order."""
+    """Run one C ABI call under the library's profiler: it succeeds and launches exactly the expected kernels, in order, each with the grid,
+    block and dynamic LDS size of tests/golden/streaming_launch.json."""
     global _FAULT
     N = _native()
     assert _FAULT is None, f"not run: the GPU reported an error in an earlier case ({_FAULT})"
@@ -101,6 +102,7 @@ def launch(c, call, kernels=None):
     ran = [SR.kernel_id(r[0]) for r in N.prof_records()]
     want = list(c.kernels if kernels is None else kernels)
     assert ran == want, f"{c.id}: launched {ran}, expected {want} ({c.why})"
+    SR.check_geometry(c.id, ran, N.prof_launches())
 
 
 def check(c, g, ref, S, nterms, what=""):
@@ -584,6 +586,16 @@ def test_contract_rejections_launch_nothing(rej):
             rc = L.sgx_colsum(p(x), p(out.t), 1.0, p(ws), L.sgx_colsum_ws_bytes(64, 48) - 1, 64, 48, 0, st)
         elif rid == "rgb_wgrad-C48":
             rc = L.sgx_rgb_wgrad(p(img), p(x), p(out.t), 48, 1, 1.0, p(ws), L.sgx_rgb_wgrad_ws_bytes(64, 48), 64, 48, 0, st)
+        elif rid.endswith("-dtype7"):                       # valid buffers and shapes (64 pixels x 48 channels, 8 x 8 images), dtype 7
+            rc = {"sgx_bias_act": lambda: L.sgx_bias_act(p(x), None, 1.0, p(out.t), 64, 48, 1, 7, st),
+                  "sgx_pool2": lambda: L.sgx_pool2(p(x), p(out.t), 1, 8, 8, 48, 1.0, 7, st),
+                  "sgx_up2": lambda: L.sgx_up2(p(x), p(out.t), 1, 8, 8, 48, 1.0, 7, st),
+                  "sgx_up2_add": lambda: L.sgx_up2_add(p(x[:16]), p(x), p(out.t), 1, 4, 4, 48, 1.0, 7, st),
+                  "sgx_colsum": lambda: L.sgx_colsum(p(x), p(out.t), 1.0, p(ws), L.sgx_colsum_ws_bytes(64, 48), 64, 48, 7, st),
+                  "sgx_rgb_in": lambda: L.sgx_rgb_in(p(img), p(x), 1, 3, 1.0, None, p(out.t), 64, 48, 7, st),
+                  "sgx_rgb_out": lambda: L.sgx_rgb_out(p(x), p(x), 48, 1, 1.0, None, p(out.t), 64, 48, 7, st),
+                  "sgx_lrelu_bwd_bits": lambda: L.sgx_lrelu_bwd_bits(p(xb), p(xb), p(out.t), 64 * 48, 0.2, 1.0, None, 7, st),
+                  "sgx_img_in": lambda: L.sgx_img_in(p(x), p(x), 4, 1, 4, 1.0, None, p(out.t), 64, 48, 7, st)}[entry]()
         else:
             w = rnd((3 * 4104,), F32, 52); xw = rnd((4, 4104), F32, 53)
             rc = L.sgx_rgb_out(p(xw), p(w), 4104, 1, 1.0, None, p(out.t), 4, 4104, 0, st)

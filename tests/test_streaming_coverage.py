@@ -32,6 +32,9 @@ ROWS = {"sgx_bias_act": 10, "sgx_lrelu_bwd": 7, "sgx_lrelu_bwd_bits": 3, "sgx_ax
         "sgx_blur_kxk": 18, "sgx_pool2": 10, "sgx_up2": 10, "sgx_up2_add": 7, "sgx_downsample_fade_rgb": 3, "sgx_images_u8_to_nhwc": 8, "sgx_colsum": 16,
         "sgx_rgb_in": 18, "sgx_rgb_in_add": 5, "sgx_rgb_out": 26, "sgx_rgb_out_fade": 6, "sgx_rgb_wgrad": 15, "sgx_fade_rgb_bwd2": 1, "sgx_fade_rgb_bwd": 3, "sgx_rgb_out_epi": 2, "sgx_rgb_wgrad_epi": 2,
         "sgx_sumsq_f32": 3, "sgx_scale_dev_f32": 5, "sgx_pixelnorm_fwd": 3, "sgx_pixelnorm_bwd": 3}
+# ... and rejection rows per entry point (streaming_ref.REJECTIONS)
+REJECTION_ROWS = {"sgx_bias_act": 2, "sgx_blur_kxk": 1, "sgx_colsum": 2, "sgx_rgb_wgrad": 1, "sgx_rgb_out": 2, "sgx_pool2": 1, "sgx_up2": 1, "sgx_up2_add": 1,
+                  "sgx_rgb_in": 1, "sgx_lrelu_bwd_bits": 1, "sgx_img_in": 1}
 
 
 def launch_sites(path):
@@ -82,7 +85,7 @@ def all_sites():
 
 def test_every_launch_site_is_claimed_or_excused():
     pw, sm = all_sites()
-    assert len(pw) > 60 and len(sm) > 20, (len(pw), len(sm))        # the scan found the launchers
+    assert len(pw) == 52 and len(sm) == 28, (len(pw), len(sm))      # the scan found the launchers: every site of the two files
     assert unclaimed(pw, SR.CASES, SR.EXCLUDED_SITES) == []
     assert unclaimed(sm, SR.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) == []
     # the excuses name sites that exist, the covered small.hip kernels are there, and every reason is written down
@@ -107,6 +110,8 @@ def test_a_new_kernel_or_a_dropped_row_is_noticed():
     no_bf16_m3 = [c for c in SR.CASES if not c.kernels[0].startswith("blur3x3_kernel<bf16_t, 3,")]
     assert unclaimed(pw, no_bf16_m3, SR.EXCLUDED_SITES) == ["blur3x3_kernel<T, 3, ROWS> for ['bf16_t']"]
     assert dict(collections.Counter(c.entry for c in SR.CASES)) == ROWS
+    assert dict(collections.Counter(r[1] for r in SR.REJECTIONS)) == REJECTION_ROWS
+    assert len({r[0] for r in SR.REJECTIONS}) == len(SR.REJECTIONS)
 
 
 def test_case_table_shapes_select_what_they_say():
