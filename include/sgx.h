@@ -473,7 +473,10 @@ int sgx_logistic_loss(const float* fake, int n_fake, const float* real, int n_re
                       float* g_fake, float* g_real, void* stream);
 /* C[M][N] = alpha * op(A) * op(B) (+ beta*C), row-major fp32, MFMA f32 16x16x4.  EqualizedLinear
  * (models/CustomLayers.py:99-103: F.linear(x, W*w_mul)) and its gradients.  ta/tb: 0 = as stored, 1 = transposed:
- *   ta=0: A is [M][K], ta=1: A is [K][M];  tb=0: B is [K][N], tb=1: B is [N][K].                                      */
+ *   ta=0: A is [M][K], ta=1: A is [K][M];  tb=0: B is [K][N], tb=1: B is [N][K].
+ * Alignment: 4 bytes is enough for every pointer of the GEMM and the three sgx_linear_* calls.  The 16-byte operand loads (and the
+ * outer-product kernel for K <= 4) are taken only where the operand they read is 16-byte aligned; a pointer 4 bytes off gets the
+ * scalar loads of the same k, and the same bits.                                                                      */
 size_t sgx_gemm_ws_bytes(int M, int N, int K);
 int sgx_gemm_f32(const float* A, const float* Bm, float* C, int M, int N, int K, int ta, int tb, float alpha,
                  void* ws, size_t ws_bytes, void* stream);
@@ -492,7 +495,9 @@ int sgx_linear_bwd_param(const float* gy, const float* y_act, const float* x, fl
  *   [W (fp32 [N][D]), bias (fp32 [N] or 0), N, y offset in elements (= B * sum of earlier N), first tile (16 outputs per
  *    tile), w_mul as fp32 bits, b_mul as fp32 bits, layer index into lm];  total_tiles = sum of ceil(N/16).
  * y / gy: flat, group g at its offset as [B][N_g].  glm: [L][B][D] (rows of layers without a group are not written).
- * dw: flat [sum N][D], db: flat [sum N] (nullable).  B <= 32, D % 64 == 0. */
+ * dw: flat [sum N][D], db: flat [sum N] (nullable).  B <= 32, D % 64 == 0 (SGX_EUNSUPPORTED otherwise).
+ * sgx_style_fwd reads lm and the weight rows with 16-byte loads: lm must be 16-byte aligned (SGX_EINVAL otherwise), and so must every W
+ * in the table, which lives in device memory and is not checked.  The two backward calls need 4-byte alignment only. */
 #define SGX_STYLE_ROW 8
 int sgx_style_fwd(const float* lm, const void* table, float* y, int G, int B, int D, int total_tiles, void* stream);
 int sgx_style_bwd_data(const float* gy, const void* table, float* glm, int G, int B, int D, int max_n, void* stream);

@@ -240,7 +240,9 @@ extern "C" int sgx_mbstd_bwd2(const void* ggx, const void* dy, const void* x, vo
 //   bias   : C = act(alpha * A B + bscale * bias[column])      -- bias and LeakyReLU folded into the store
 //   colsum : colsum[row of C] = cscale * sum_k A'[row][k]      -- with A = gy^T this is the bias gradient, out of the
 //            same launch as the weight gradient (written by the blocks of column tile 0)
-struct GemmFuse { const float* amask; const float* bias; float bscale; int act; float* colsum; float cscale; };
+//   vec    : set by gemm_launch, not by the entry points: bit 0 = A (and amask) are 16-byte aligned, bit 1 = B is.  The 16-byte operand
+//            loads below are taken only then; a pointer 4 bytes off gets the scalar loads of the same k, hence the same bits
+struct GemmFuse { const float* amask; const float* bias; float bscale; int act; float* colsum; float cscale; unsigned vec; };
 // One 16-k step of a lane: its four operand values a4 (row ic of op(A), k = kk..kk+3) and b4 (column jc of op(B)).  No branch depends
 // on the lane: rows / columns beyond the matrix are read at the clamped index ic / jc (their products land in output rows / columns
 // that are never stored), and in the K tail (TAIL) a k beyond ke is read at ke - 1 and replaced by zero.  That lets the compiler issue
@@ -327,7 +329,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     const size_t arow = ic * sa_i, bcol = jc * sb_j;
     // 16 k per step: lane group q owns k = k0+4q..+3 (any k order is valid as long as A and B agree), so an
     // operand whose k axis is contiguous is fetched with one 16-byte load per lane instead of four 4-byte ones.
-    const bool va = !ta && (K % 4 == 0), vb = tb && (K % 4 == 0);
+    const bool va = !ta && (K % 4 == 0) && (fu.vec & 1), vb = tb && (K % 4 == 0) && (fu.vec & 2);
     f32x4 acc;
 #define GEMM_SLICE(VA, VB, MK) acc = gemm_wave_slice<U, VA, VB, MK>(A, fu.amask, Bm, arow, sa_k, bcol, sb_k, kb, ke, q)
     if (fu.amask) {
@@ -433,6 +435,7 @@ static int gemm_launch(const float* A, const float* Bm, float* C, int M, int N, 
         SGX_LAUNCH_CHECK("gemm_outer");
         return 0;
     }
+    fu.vec = ((((uintptr_t)A | (uintptr_t)fu.amask) % 16 == 0) ? 1u : 0u) | (((uintptr_t)Bm % 16 == 0) ? 2u : 0u);
     // A wave's K slice of 128 or more (K = 512 unsplit, every split-K launch) runs with the loads of 8 steps in flight: 106 registers.
     // Shorter slices never enter that loop, and their launches are many small blocks (K = 8: 1024 of them) that want the
     // 8 blocks per CU a small register file allows, so they get the instantiation without the unrolled loop.
@@ -678,6 +681,9 @@ static int style_check(int G, int B, int D) {
 }
 extern "C" int sgx_style_fwd(const float* lm, const void* table, float* y, int G, int B, int D, int total_tiles, void* stream) {
     int rc = style_check(G, B, D); if (rc) return rc;
+    // the kernel stages lm and reads the weight rows with 16-byte loads.  lm is checked here; the W pointers live in the device table,
+    // which the host does not read: their alignment is the caller's contract (include/sgx.h)
+    SGX_REQUIRE((uintptr_t)lm % 16 == 0, SGX_EINVAL, "style_fwd: lm must be 16-byte aligned");
     SGX_NOTE(0.0, 0.0, "style_fwd G%d B%d", G, B);
     if (B <= 4) hipLaunchKernelGGL(style_fwd_kernel<4>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
     else if (B <= 8) hipLaunchKernelGGL(style_fwd_kernel<8>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import gpu_util
+import small_ref as SM
 import streaming_ref as SR
 from oracle import stylegan_oracle as O
 
@@ -18,15 +19,11 @@ CSRC = os.path.join(ROOT, "stylegan", "pytorch_amd", "csrc")
 SITE = re.compile(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_][A-Za-z_0-9]*)\s*(<[^>()]*>)?")
 LITERAL = re.compile(r"^(-?\d+|true|false|float|bf16_t)$")
 
-# Kernels of small.hip that are not streaming kernels: each has its own kernel-level tests
-SMALL_HIP_OTHER = {
-    "mbstd_fwd_kernel": "minibatch stddev: tests/test_gpu_kernels.py", "mbstd_bwd_kernel": "minibatch stddev: tests/test_gpu_kernels.py",
-    "mbstd_bwd2_kernel": "minibatch stddev: tests/test_gpu_kernels.py", "gemm_outer_kernel": "fp32 GEMM: tests/test_gpu_small_kernels.py",
-    "kern": "fp32 GEMM (kernel chosen through a function pointer): tests/test_gpu_small_kernels.py",
-    "gemm_splitk_reduce": "fp32 GEMM: tests/test_gpu_small_kernels.py", "style_fwd_kernel": "style affines: tests/test_gpu_small_kernels.py",
-    "style_bwd_data_kernel": "style affines: tests/test_gpu_small_kernels.py", "style_bwd_param_kernel": "style affines: tests/test_gpu_small_kernels.py",
-    "logistic_loss_kernel": "loss head, one wave: tests/test_gpu_small_kernels.py",
-}
+# Kernels of small.hip that are not streaming kernels are claimed by the rows of tests/small_ref.py, site by site and instantiation by
+# instantiation (tests/test_gpu_small_paths.py runs them; the loss head's older rel-L2 test is in tests/test_gpu_fusions.py).  The scan below takes
+# those rows beside streaming_ref's; the one site it cannot read is the tile GEMM's, started through a function pointer
+SMALL_HIP_OTHER = {SM.GEMM_POINTER: "fp32 tile GEMM, started through a function pointer: tests/test_small_coverage.py reads the two instantiations it can hold "
+                                    "from its initialiser and finds both in rows of small_ref.CASES"}
 # Rows per entry point.  A row is a launch path someone decided to cover: dropping one has to be a decision made here too.
 ROWS = {"sgx_bias_act": 10, "sgx_lrelu_bwd": 7, "sgx_lrelu_bwd_bits": 3, "sgx_axpby": 11, "sgx_axpby_dev": 10, "sgx_blur3x3_act": 43, "sgx_blur3x3_bits": 8,
         "sgx_blur_kxk": 18, "sgx_pool2": 10, "sgx_up2": 10, "sgx_up2_add": 7, "sgx_downsample_fade_rgb": 3, "sgx_images_u8_to_nhwc": 8, "sgx_colsum": 16,
@@ -87,7 +84,8 @@ def test_every_launch_site_is_claimed_or_excused():
     pw, sm = all_sites()
     assert len(pw) == 52 and len(sm) == 28, (len(pw), len(sm))      # the scan found the launchers: every site of the two files
     assert unclaimed(pw, SR.CASES, SR.EXCLUDED_SITES) == []
-    assert unclaimed(sm, SR.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) == []
+    assert unclaimed(sm, SR.CASES + SM.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) == []
+    assert unclaimed(sm, SR.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) != []                    # ... a claim by the rows, no longer an excuse by name
     # the excuses name sites that exist, the covered small.hip kernels are there, and every reason is written down
     texts = {s[0] + s[1] for s in pw + sm}
     assert set(SR.EXCLUDED_SITES) <= texts, set(SR.EXCLUDED_SITES) - texts
