@@ -478,6 +478,18 @@ int sgx_logistic_loss(const float* fake, int n_fake, const float* real, int n_re
  * outer-product kernel for K <= 4) are taken only where the operand they read is 16-byte aligned; a pointer 4 bytes off gets the
  * scalar loads of the same k, and the same bits.                                                                      */
 size_t sgx_gemm_ws_bytes(int M, int N, int K);
+/* Host-only query: what sgx_gemm_f32 (fuse 0) or one of the three sgx_linear_* calls will launch for this shape.  The launcher executes
+ * the same plan.  fuse: bit 0 = an activation mask on A (sgx_linear_bwd_data / _param with y_act), bit 1 = bias, activation or db fused
+ * into the launch;  ws_bytes: the workspace held, 0 for NULL (the sgx_linear_* calls have none);  align: bit 0 = A and the mask are
+ * 16-byte aligned, bit 1 = B is, bit 2 = C is.  out[SGX_GEMM_PLAN_INTS]:
+ *   [0]  the kernel: 0 gemm_outer_kernel (K <= 4, B as stored, N % 4 == 0, nothing fused, B and C aligned), 1 gemm_f32_kernel<1>,
+ *        2 gemm_f32_kernel<8> (a split's K of 512 or more)
+ *   [1]  K splits; above 1 the partials go to the workspace and gemm_splitk_reduce follows (never with bit 1 of fuse or a short workspace)
+ *   [2..4]  that kernel's grid x, y, z;  [5] the grid of gemm_splitk_reduce, 0 when unsplit
+ *   [6]  the 16-byte operand loads the tile kernel may take: bit 0 = of A (and the mask), bit 1 = of B (0 for the outer-product kernel)
+ * Returns 0, or SGX_EINVAL for a shape that is not positive. */
+#define SGX_GEMM_PLAN_INTS 7
+int sgx_gemm_plan(int M, int N, int K, int ta, int tb, int fuse, size_t ws_bytes, int align, int* out);
 int sgx_gemm_f32(const float* A, const float* Bm, float* C, int M, int N, int K, int ta, int tb, float alpha,
                  void* ws, size_t ws_bytes, void* stream);
 /* EqualizedLinear (models/CustomLayers.py:64-103) of the mapping network and the style affines, three launches:

@@ -1,5 +1,8 @@
 // Small fp32 pieces: PixelNorm rows, minibatch-stddev (forward / backward / second-order backward for R1),
 // and the MFMA fp32 GEMM behind EqualizedLinear (mapping network, style affine maps, discriminator head).
+// Launch layer: an entry point checks its arguments, decides once -- mbstd_run (grid, dtype -> T through sgx_by_dtype), style_mb (batch -> MB
+// through sgx_by_int), gemm_plan (kernel, splits, grids, vec: what sgx_gemm_plan reports without launching) -- and every kernel has one
+// hipLaunchKernelGGL site, spelled with the parameter (T, MB, U) where the decision is a template argument.
 #include "common.h"
 
 // ---------------------------------------------------------------- PixelNorm over the feature dim of [B][C]
@@ -205,30 +208,33 @@ static int mbstd_check(int B, int C, int Cpad) {
     SGX_REQUIRE(Cpad > C, SGX_EINVAL, "mbstd: Cpad must exceed C");
     return 0;
 }
-extern "C" int sgx_mbstd_fwd(const void* x, void* y, int B, int HW, int C, int Cpad, int dtype, void* stream) {
+// The three entry points: the shape check, the (M, MBSTD_NB) grid and dtype -> T, once; f(T{}, grid, stream) holds the kernel's launch site
+template <typename F> static int mbstd_run(const char* name, int B, int C, int Cpad, int dtype, void* stream, F f) {
     int rc = mbstd_check(B, C, Cpad); if (rc) return rc;
-    const int M = B / (B < 4 ? B : 4);
-    if (dtype == SGX_F32) hipLaunchKernelGGL(mbstd_fwd_kernel<float>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const float*)x, (float*)y, B, HW, C, Cpad);
-    else hipLaunchKernelGGL(mbstd_fwd_kernel<bf16_t>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, B, HW, C, Cpad);
-    SGX_LAUNCH_CHECK("mbstd_fwd");
-    return 0;
+    return sgx_by_dtype(dtype, name, [&](auto t) -> int {
+        f(t, dim3(B / (B < 4 ? B : 4), MBSTD_NB), (hipStream_t)stream);
+        SGX_LAUNCH_CHECK(name);
+        return 0;
+    });
+}
+extern "C" int sgx_mbstd_fwd(const void* x, void* y, int B, int HW, int C, int Cpad, int dtype, void* stream) {
+    return mbstd_run("mbstd_fwd", B, C, Cpad, dtype, stream, [&](auto t, dim3 grid, hipStream_t st) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mbstd_fwd_kernel<T>, grid, dim3(1024), 0, st, as<T>(x), as<T>(y), B, HW, C, Cpad);
+    });
 }
 extern "C" int sgx_mbstd_bwd(const void* dy, const void* x, void* dx, int B, int HW, int C, int Cpad, int dtype, void* stream) {
-    int rc = mbstd_check(B, C, Cpad); if (rc) return rc;
-    const int M = B / (B < 4 ? B : 4);
-    if (dtype == SGX_F32) hipLaunchKernelGGL(mbstd_bwd_kernel<float>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const float*)dy, (const float*)x, (float*)dx, B, HW, C, Cpad);
-    else hipLaunchKernelGGL(mbstd_bwd_kernel<bf16_t>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, B, HW, C, Cpad);
-    SGX_LAUNCH_CHECK("mbstd_bwd");
-    return 0;
+    return mbstd_run("mbstd_bwd", B, C, Cpad, dtype, stream, [&](auto t, dim3 grid, hipStream_t st) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mbstd_bwd_kernel<T>, grid, dim3(1024), 0, st, as<T>(dy), as<T>(x), as<T>(dx), B, HW, C, Cpad);
+    });
 }
 extern "C" int sgx_mbstd_bwd2(const void* ggx, const void* dy, const void* x, void* ddy, void* gx, int B, int HW, int C, int Cpad,
                               int dtype, void* stream) {
-    int rc = mbstd_check(B, C, Cpad); if (rc) return rc;
-    const int M = B / (B < 4 ? B : 4);
-    if (dtype == SGX_F32) hipLaunchKernelGGL(mbstd_bwd2_kernel<float>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const float*)ggx, (const float*)dy, (const float*)x, (float*)ddy, (float*)gx, B, HW, C, Cpad);
-    else hipLaunchKernelGGL(mbstd_bwd2_kernel<bf16_t>, dim3(M, MBSTD_NB), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)ggx, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)ddy, (bf16_t*)gx, B, HW, C, Cpad);
-    SGX_LAUNCH_CHECK("mbstd_bwd2");
-    return 0;
+    return mbstd_run("mbstd_bwd2", B, C, Cpad, dtype, stream, [&](auto t, dim3 grid, hipStream_t st) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mbstd_bwd2_kernel<T>, grid, dim3(1024), 0, st, as<T>(ggx), as<T>(dy), as<T>(x), as<T>(ddy), as<T>(gx), B, HW, C, Cpad);
+    });
 }
 
 // ---------------------------------------------------------------- fp32 GEMM on v_mfma_f32_16x16x4_f32
@@ -240,7 +246,7 @@ extern "C" int sgx_mbstd_bwd2(const void* ggx, const void* dy, const void* x, vo
 //   bias   : C = act(alpha * A B + bscale * bias[column])      -- bias and LeakyReLU folded into the store
 //   colsum : colsum[row of C] = cscale * sum_k A'[row][k]      -- with A = gy^T this is the bias gradient, out of the
 //            same launch as the weight gradient (written by the blocks of column tile 0)
-//   vec    : set by gemm_launch, not by the entry points: bit 0 = A (and amask) are 16-byte aligned, bit 1 = B is.  The 16-byte operand
+//   vec    : set by gemm_launch (from gemm_plan), not by the entry points: bit 0 = A (and amask) are 16-byte aligned, bit 1 = B is.  The 16-byte operand
 //            loads below are taken only then; a pointer 4 bytes off gets the scalar loads of the same k, hence the same bits
 struct GemmFuse { const float* amask; const float* bias; float bscale; int act; float* colsum; float cscale; unsigned vec; };
 // One 16-k step of a lane: its four operand values a4 (row ic of op(A), k = kk..kk+3) and b4 (column jc of op(B)).  No branch depends
@@ -420,36 +426,53 @@ extern "C" size_t sgx_gemm_ws_bytes(int M, int N, int K) {
     const int s = gemm_splits(M, N, K);
     return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
 }
-static int gemm_launch(const float* A, const float* Bm, float* C, int M, int N, int K, int ta, int tb, float alpha, GemmFuse fu, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
-    SGX_REQUIRE(M > 0 && N > 0 && K > 0, SGX_EINVAL, "gemm: bad shape %d %d %d", M, N, K);
+// Everything one GEMM call will do: the ints of sgx_gemm_plan (include/sgx.h) in its order.  unroll: 0 = gemm_outer_kernel, else U of
+// gemm_f32_kernel<U>, 1 or 8 (reported as kind 1 / 2); (gx, gy, gz): that kernel's grid; reduce_gx: gemm_splitk_reduce's, 0 when unsplit.
+//   fuse  : bit 0 = amask given, bit 1 = bias, activation or colsum given (those are not carried through a split)
+//   align : bit 0 = A and amask 16-byte aligned, bit 1 = B, bit 2 = C;  ws_bytes: what the caller holds, 0 for a NULL workspace
+struct GemmPlan { int unroll, splits, gx, gy, gz, reduce_gx, vec; };
+static GemmPlan gemm_plan(int M, int N, int K, int ta, int tb, int fuse, size_t ws_bytes, int align) {
+    if (K <= 4 && !tb && N % 4 == 0 && !fuse && (align & 6) == 6) return GemmPlan{0, 1, (int)(((size_t)M * (N / 4) + 255) / 256), 1, 1, 0, 0};
     int splits = gemm_splits(M, N, K);
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * M * N * sizeof(float) || fu.bias || fu.act || fu.colsum)) splits = 1;
-    SGX_NOTE(2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N), "gemm %dx%dx%d t%d%d%s", M, N, K, ta, tb,
-             fu.amask || fu.bias || fu.colsum ? " fused" : "");
-    const bool fused = fu.amask || fu.bias || fu.act || fu.colsum;
-    if (K <= 4 && !tb && N % 4 == 0 && !fused && ((uintptr_t)Bm | (uintptr_t)C) % 16 == 0) {
-        const size_t n = (size_t)M * (N / 4);
-        hipLaunchKernelGGL(gemm_outer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, Bm, C, M, N, K, ta ? (size_t)1 : (size_t)K,
-                           ta ? (size_t)M : (size_t)1, alpha);
-        SGX_LAUNCH_CHECK("gemm_outer");
-        return 0;
-    }
-    fu.vec = ((((uintptr_t)A | (uintptr_t)fu.amask) % 16 == 0) ? 1u : 0u) | (((uintptr_t)Bm % 16 == 0) ? 2u : 0u);
+    if (splits > 1 && (ws_bytes < (size_t)splits * M * N * sizeof(float) || (fuse & 2))) splits = 1;
     // A wave's K slice of 128 or more (K = 512 unsplit, every split-K launch) runs with the loads of 8 steps in flight: 106 registers.
     // Shorter slices never enter that loop, and their launches are many small blocks (K = 8: 1024 of them) that want the
     // 8 blocks per CU a small register file allows, so they get the instantiation without the unrolled loop.
-    const int ksplit = (K + splits - 1) / splits;
-    auto kern = ksplit >= 512 ? gemm_f32_kernel<8> : gemm_f32_kernel<1>;
-    if (splits == 1) {
-        hipLaunchKernelGGL(kern, dim3((N + 15) / 16, (M + 15) / 16, 1), dim3(256), 0, st, A, Bm, C, M, N, K, ta, tb, alpha, fu);
-        SGX_LAUNCH_CHECK("gemm_f32");
+    const int unroll = (K + splits - 1) / splits >= 512 ? 8 : 1;
+    return GemmPlan{unroll, splits, (N + 15) / 16, (M + 15) / 16, splits, splits > 1 ? (M * N + 255) / 256 : 0, align & 3};
+}
+extern "C" int sgx_gemm_plan(int M, int N, int K, int ta, int tb, int fuse, size_t ws_bytes, int align, int* out) {
+    SGX_REQUIRE(M > 0 && N > 0 && K > 0, SGX_EINVAL, "gemm: bad shape %d %d %d", M, N, K);
+    SGX_REQUIRE(out, SGX_EINVAL, "gemm_plan: out is NULL");
+    const GemmPlan p = gemm_plan(M, N, K, ta, tb, fuse, ws_bytes, align);
+    const int v[SGX_GEMM_PLAN_INTS] = {p.unroll == 8 ? 2 : p.unroll, p.splits, p.gx, p.gy, p.gz, p.reduce_gx, p.vec};
+    for (int i = 0; i < SGX_GEMM_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
+}
+static int gemm_launch(const float* A, const float* Bm, float* C, int M, int N, int K, int ta, int tb, float alpha, GemmFuse fu, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
+    SGX_REQUIRE(M > 0 && N > 0 && K > 0, SGX_EINVAL, "gemm: bad shape %d %d %d", M, N, K);
+    const GemmPlan p = gemm_plan(M, N, K, ta, tb, (fu.amask ? 1 : 0) | (fu.bias || fu.act || fu.colsum ? 2 : 0), ws ? ws_bytes : 0,
+                                 (sgx_aligned16(A) && sgx_aligned16(fu.amask) ? 1 : 0) | (sgx_aligned16(Bm) ? 2 : 0) | (sgx_aligned16(C) ? 4 : 0));
+    SGX_NOTE(2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N), "gemm %dx%dx%d t%d%d%s", M, N, K, ta, tb,
+             fu.amask || fu.bias || fu.colsum ? " fused" : "");
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (!p.unroll) {
+        hipLaunchKernelGGL(gemm_outer_kernel, grid, dim3(256), 0, st, A, Bm, C, M, N, K, ta ? (size_t)1 : (size_t)K, ta ? (size_t)M : (size_t)1, alpha);
+        SGX_LAUNCH_CHECK("gemm_outer");
         return 0;
     }
-    hipLaunchKernelGGL(kern, dim3((N + 15) / 16, (M + 15) / 16, splits), dim3(256), 0, st, A, Bm, (float*)ws, M, N, K, ta, tb, 1.0f, fu);
+    fu.vec = p.vec;
+    const bool split = p.splits > 1;                           // the partials go to the workspace unscaled: alpha is the reduce's
+    sgx_by_int<1, 8>(p.unroll, [&](auto u) {
+        constexpr int U = u();
+        hipLaunchKernelGGL(gemm_f32_kernel<U>, grid, dim3(256), 0, st, A, Bm, split ? (float*)ws : C, M, N, K, ta, tb, split ? 1.0f : alpha, fu);
+    });
     SGX_LAUNCH_CHECK("gemm_f32");
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3((M * N + 255) / 256), dim3(256), 0, st, (const float*)ws, C, M * N, splits, alpha);
-    SGX_LAUNCH_CHECK("gemm_splitk_reduce");
+    if (split) {
+        hipLaunchKernelGGL(gemm_splitk_reduce, dim3(p.reduce_gx), dim3(256), 0, st, (const float*)ws, C, M * N, p.splits, alpha);
+        SGX_LAUNCH_CHECK("gemm_splitk_reduce");
+    }
     return 0;
 }
 extern "C" int sgx_gemm_f32(const float* A, const float* Bm, float* C, int M, int N, int K, int ta, int tb, float alpha, void* ws,
@@ -679,28 +702,30 @@ static int style_check(int G, int B, int D) {
     SGX_REQUIRE(G > 0 && B > 0 && B <= STYLE_MAXB && D > 0 && D % 64 == 0, SGX_EUNSUPPORTED, "style affines: G=%d B=%d D=%d", G, B, D);
     return 0;
 }
+// the MB a batch runs with: the smallest of the instantiations 4, 8, 16, 32 (the sgx_by_int lists below) that holds it
+static_assert(STYLE_MAXB == 32, "style_mb and the sgx_by_int<4, 8, 16, 32> lists end at STYLE_MAXB");
+static int style_mb(int B) { return B <= 4 ? 4 : (B <= 8 ? 8 : (B <= 16 ? 16 : 32)); }
 extern "C" int sgx_style_fwd(const float* lm, const void* table, float* y, int G, int B, int D, int total_tiles, void* stream) {
     int rc = style_check(G, B, D); if (rc) return rc;
     // the kernel stages lm and reads the weight rows with 16-byte loads.  lm is checked here; the W pointers live in the device table,
     // which the host does not read: their alignment is the caller's contract (include/sgx.h)
     SGX_REQUIRE((uintptr_t)lm % 16 == 0, SGX_EINVAL, "style_fwd: lm must be 16-byte aligned");
     SGX_NOTE(0.0, 0.0, "style_fwd G%d B%d", G, B);
-    if (B <= 4) hipLaunchKernelGGL(style_fwd_kernel<4>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
-    else if (B <= 8) hipLaunchKernelGGL(style_fwd_kernel<8>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
-    else if (B <= 16) hipLaunchKernelGGL(style_fwd_kernel<16>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
-    else hipLaunchKernelGGL(style_fwd_kernel<32>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
+    sgx_by_int<4, 8, 16, 32>(style_mb(B), [&](auto mb) {
+        constexpr int MB = mb();
+        hipLaunchKernelGGL(style_fwd_kernel<MB>, dim3(total_tiles), dim3(256), (size_t)B * D * sizeof(float), (hipStream_t)stream, lm, (const long long*)table, y, G, B, D);
+    });
     SGX_LAUNCH_CHECK("style_fwd");
     return 0;
 }
 extern "C" int sgx_style_bwd_data(const float* gy, const void* table, float* glm, int G, int B, int D, int max_n, void* stream) {
     int rc = style_check(G, B, D); if (rc) return rc;
-    const int mb = B <= 4 ? 4 : (B <= 8 ? 8 : (B <= 16 ? 16 : 32));
-    const size_t a = (size_t)mb * max_n, b = (size_t)4 * B * 64;  // the transposed gy image [max_n][MB], then the wave partials
+    const size_t a = (size_t)style_mb(B) * max_n, b = (size_t)4 * B * 64;  // the transposed gy image [max_n][MB], then the wave partials
     SGX_NOTE(0.0, 0.0, "style_bwd_data G%d B%d", G, B);
-    if (B <= 4) hipLaunchKernelGGL(style_bwd_data_kernel<4>, dim3(D / 64, G), dim3(256), (a > b ? a : b) * sizeof(float), (hipStream_t)stream, gy, (const long long*)table, glm, G, B, D);
-    else if (B <= 8) hipLaunchKernelGGL(style_bwd_data_kernel<8>, dim3(D / 64, G), dim3(256), (a > b ? a : b) * sizeof(float), (hipStream_t)stream, gy, (const long long*)table, glm, G, B, D);
-    else if (B <= 16) hipLaunchKernelGGL(style_bwd_data_kernel<16>, dim3(D / 64, G), dim3(256), (a > b ? a : b) * sizeof(float), (hipStream_t)stream, gy, (const long long*)table, glm, G, B, D);
-    else hipLaunchKernelGGL(style_bwd_data_kernel<32>, dim3(D / 64, G), dim3(256), (a > b ? a : b) * sizeof(float), (hipStream_t)stream, gy, (const long long*)table, glm, G, B, D);
+    sgx_by_int<4, 8, 16, 32>(style_mb(B), [&](auto mb) {
+        constexpr int MB = mb();
+        hipLaunchKernelGGL(style_bwd_data_kernel<MB>, dim3(D / 64, G), dim3(256), (a > b ? a : b) * sizeof(float), (hipStream_t)stream, gy, (const long long*)table, glm, G, B, D);
+    });
     SGX_LAUNCH_CHECK("style_bwd_data");
     return 0;
 }
@@ -708,10 +733,10 @@ extern "C" int sgx_style_bwd_param(const float* gy, const float* lm, const void*
                                    int total_tiles, void* stream) {
     int rc = style_check(G, B, D); if (rc) return rc;
     SGX_NOTE(0.0, 0.0, "style_bwd_param G%d B%d", G, B);
-    if (B <= 4) hipLaunchKernelGGL(style_bwd_param_kernel<4>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, gy, lm, (const long long*)table, dw, db, G, B, D);
-    else if (B <= 8) hipLaunchKernelGGL(style_bwd_param_kernel<8>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, gy, lm, (const long long*)table, dw, db, G, B, D);
-    else if (B <= 16) hipLaunchKernelGGL(style_bwd_param_kernel<16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, gy, lm, (const long long*)table, dw, db, G, B, D);
-    else hipLaunchKernelGGL(style_bwd_param_kernel<32>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, gy, lm, (const long long*)table, dw, db, G, B, D);
+    sgx_by_int<4, 8, 16, 32>(style_mb(B), [&](auto mb) {
+        constexpr int MB = mb();
+        hipLaunchKernelGGL(style_bwd_param_kernel<MB>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, gy, lm, (const long long*)table, dw, db, G, B, D);
+    });
     SGX_LAUNCH_CHECK("style_bwd_param");
     return 0;
 }

@@ -131,6 +131,7 @@ SIGNATURES = {
     "sgx_scale_dev_f32": (I, [P, P, F, P, Z, P]),
     "sgx_logistic_loss": (I, [P, I, P, I, F, I, P, P, P, P]),
     "sgx_gemm_ws_bytes": (Z, [I, I, I]),
+    "sgx_gemm_plan": (I, [I, I, I, I, I, I, Z, I, P]),
     "sgx_gemm_f32": (I, [P, P, P, I, I, I, I, I, F, P, Z, P]),
     "sgx_linear_fwd": (I, [P, P, P, P, I, I, I, F, F, I, P]),
     "sgx_linear_bwd_data": (I, [P, P, P, P, I, I, I, F, P]),

@@ -93,6 +93,14 @@ def gemm_plan(M, N, K, ta, tb, mask=False, epi=False, ws_bytes=0, aligned=True):
     return GemmPlan((kern, REDUCE), launches + [((cdiv(M * N, 256), 1, 1), (256, 1, 1), 0)], splits, kper, body, tail)
 
 
+def gemm_plan_ints(pl, align):
+    """A GemmPlan as the seven ints of sgx_gemm_plan (include/sgx.h): kernel 0 / 1 / 2, splits, that kernel's grid, the reduce's grid (0 when
+    unsplit) and vec.  align: the query's own argument, whose bits 0 and 1 (A and its mask, B on 16 bytes) are the tile kernel's vec."""
+    (gx, gy, gz), _, _ = pl.launches[0]
+    kind = {OUTER: 0, K1: 1, K8: 2}[pl.kernels[0]]
+    return [kind, pl.splits, gx, gy, gz, pl.launches[1][0][0] if len(pl.launches) > 1 else 0, align & 3 if kind else 0]
+
+
 def gemm_chain(pl, mask=False, bias=False, act=False):
     """The fp32 operations on an output's longest chain.  Every product that enters an MFMA accumulator counts as one (the order inside the
     instruction is not specified): a wave's slice of kper values of k is kper of them (the outer-product kernel: K fused multiply-adds).  Then
@@ -605,6 +613,9 @@ REJECTIONS = [
     ("mbstd_fwd-Cpad-eq-C", "sgx_mbstd_fwd", EINVAL, "Cpad must exceed C", "Cpad = C: no room for the statistic"),
     ("mbstd_bwd-Cpad-lt-C", "sgx_mbstd_bwd", EINVAL, "Cpad must exceed C", "Cpad < C"),
     ("mbstd_bwd2-Cpad-eq-C", "sgx_mbstd_bwd2", EINVAL, "Cpad must exceed C", "Cpad = C"),
+    ("mbstd_fwd-dtype2", "sgx_mbstd_fwd", EINVAL, "mbstd_fwd: dtype 2", "dtype 2: neither SGX_F32 nor SGX_BF16"),
+    ("mbstd_bwd-dtype2", "sgx_mbstd_bwd", EINVAL, "mbstd_bwd: dtype 2", "dtype 2"),
+    ("mbstd_bwd2-dtype2", "sgx_mbstd_bwd2", EINVAL, "mbstd_bwd2: dtype 2", "dtype 2"),
     ("style_fwd-B33", "sgx_style_fwd", EUNSUPPORTED, "style affines", "B above STYLE_MAXB = 32"),
     ("style_bwd_data-B33", "sgx_style_bwd_data", EUNSUPPORTED, "style affines", "B = 33"),
     ("style_bwd_param-B33", "sgx_style_bwd_param", EUNSUPPORTED, "style affines", "B = 33"),
@@ -626,6 +637,3 @@ ROWS = {"sgx_gemm_f32": 44, "sgx_linear_fwd": 8, "sgx_linear_bwd_data": 9, "sgx_
 # The kernels of small.hip this table answers for (the R1 head and PixelNorm belong to streaming_ref.SMALL_HIP_COVERED)
 KERNELS = ("mbstd_fwd_kernel", "mbstd_bwd_kernel", "mbstd_bwd2_kernel", "gemm_outer_kernel", "gemm_f32_kernel", "gemm_splitk_reduce", "style_fwd_kernel", "style_bwd_data_kernel",
            "style_bwd_param_kernel", "logistic_loss_kernel")
-# gemm_launch starts the tile kernel through a function pointer: the scan of launch sites sees the pointer's name, and
-# tests/test_small_coverage.py reads the instantiations it can hold from its initialiser
-GEMM_POINTER = "kern"

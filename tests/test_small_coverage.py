@@ -42,16 +42,14 @@ def sites():
 
 def test_every_launch_site_of_small_hip_has_a_row():
     sm = sites()
-    assert len(sm) == 23, len(sm)                           # 28 in the file, 5 of them the streaming part's
-    names = {s[0] for s in sm}
-    assert names == (set(SM.KERNELS) - {"gemm_f32_kernel"}) | {SM.GEMM_POINTER}, names
-    assert TSC.unclaimed([s for s in sm if s[0] != SM.GEMM_POINTER], SM.CASES, {}) == []
-    # the tile kernel is started through a function pointer: what the pointer can hold is in its initialiser, and both are named by rows
-    init = re.search(r"auto\s+" + SM.GEMM_POINTER + r"\s*=([^;]*);", source()).group(1)
-    held = sorted(set(re.findall(r"gemm_f32_kernel<\d+>", init)))
+    assert len(sm) == 10, len(sm)                           # 15 in the file, 5 of them the streaming part's: one site per kernel of KERNELS,
+    assert sorted(s[0] for s in sm) == sorted(SM.KERNELS)   # ... mbstd 3, the GEMM's 3, the style affines 3, the logistic head 1
+    assert TSC.unclaimed(sm, SM.CASES, {}) == []
+    # the tile kernel's one site is generic in U of sgx_by_int<1, 8>: the list is read from the source, and both values are named by rows
+    (tile,) = [s for s in sm if s[0] == "gemm_f32_kernel"]
+    held = [f"gemm_f32_kernel<{v}>" for v in tile[2]["U"]]
     named = {k for c in SM.CASES for k in c.kernels}
-    assert held == [SM.K1, SM.K8] and set(held) <= named
-    assert len([s for s in sm if s[0] == SM.GEMM_POINTER]) == 2          # the unsplit and the split launch
+    assert tile[1] == "<U>" and held == [SM.K1, SM.K8] and set(held) <= named
     # every __global__ function of the file belongs to this table or to the streaming one, and every kernel a row names exists
     kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\(\d+\)\s+)?void\s+([A-Za-z_0-9]+)", source()))
     assert kernels == set(SM.KERNELS) | set(SR.SMALL_HIP_COVERED), kernels ^ (set(SM.KERNELS) | set(SR.SMALL_HIP_COVERED))
@@ -63,13 +61,16 @@ def test_every_launch_site_of_small_hip_has_a_row():
 
 
 def test_a_new_site_or_a_dropped_row_is_noticed():
-    sm = [s for s in sites() if s[0] != SM.GEMM_POINTER]
+    sm = sites()
     assert TSC.unclaimed(sm + [("style_fwd_kernel", "<64>")], SM.CASES, {}) == ["style_fwd_kernel<64>"]
     assert TSC.unclaimed(sm + [("gemm_batched_kernel", "")], SM.CASES, {}) == ["gemm_batched_kernel"]
     no_bf16_bwd2 = [c for c in SM.CASES if c.kernels != ("mbstd_bwd2_kernel<bf16_t>",)]
-    assert TSC.unclaimed(sm, no_bf16_bwd2, {}) == ["mbstd_bwd2_kernel<bf16_t>"]
+    assert TSC.unclaimed(sm, no_bf16_bwd2, {}) == ["mbstd_bwd2_kernel<T> for ['bf16_t']"]
     no_b32 = [c for c in SM.CASES if not (c.entry == "sgx_style_bwd_data" and c.args["B"] > 16)]
-    assert TSC.unclaimed(sm, no_b32, {}) == ["style_bwd_data_kernel<32>"]
+    assert TSC.unclaimed(sm, no_b32, {}) == ["style_bwd_data_kernel<MB> for [32]"]
+    # ... and either instantiation of the tile GEMM, now one site
+    assert TSC.unclaimed(sm, [c for c in SM.CASES if SM.K8 not in c.kernels], {}) == ["gemm_f32_kernel<U> for [8]"]
+    assert TSC.unclaimed(sm, [c for c in SM.CASES if SM.K1 not in c.kernels], {}) == ["gemm_f32_kernel<U> for [1]"]
 
 
 def test_rows_reach_the_branches_they_are_there_for():
@@ -215,6 +216,9 @@ def reject(L, id):
         "mbstd_fwd-Cpad-eq-C": lambda: L.sgx_mbstd_fwd(P, P, 4, 16, 8, 8, 0, st),
         "mbstd_bwd-Cpad-lt-C": lambda: L.sgx_mbstd_bwd(P, P, P, 4, 16, 8, 7, 1, st),
         "mbstd_bwd2-Cpad-eq-C": lambda: L.sgx_mbstd_bwd2(P, P, P, P, P, 4, 16, 8, 8, 0, st),
+        "mbstd_fwd-dtype2": lambda: L.sgx_mbstd_fwd(P, P, 4, 16, 8, 9, 2, st),
+        "mbstd_bwd-dtype2": lambda: L.sgx_mbstd_bwd(P, P, P, 4, 16, 8, 9, 2, st),
+        "mbstd_bwd2-dtype2": lambda: L.sgx_mbstd_bwd2(P, P, P, P, P, 4, 16, 8, 9, 2, st),
         "style_fwd-B33": lambda: L.sgx_style_fwd(P, P, P, 2, 33, 512, 4, st),
         "style_bwd_data-B33": lambda: L.sgx_style_bwd_data(P, P, P, 2, 33, 512, 32, st),
         "style_bwd_param-B33": lambda: L.sgx_style_bwd_param(P, P, P, P, P, 2, 33, 512, 4, st),

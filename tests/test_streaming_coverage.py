@@ -21,9 +21,8 @@ LITERAL = re.compile(r"^(-?\d+|true|false|float|bf16_t)$")
 
 # Kernels of small.hip that are not streaming kernels are claimed by the rows of tests/small_ref.py, site by site and instantiation by
 # instantiation (tests/test_gpu_small_paths.py runs them; the loss head's older rel-L2 test is in tests/test_gpu_fusions.py).  The scan below takes
-# those rows beside streaming_ref's; the one site it cannot read is the tile GEMM's, started through a function pointer
-SMALL_HIP_OTHER = {SM.GEMM_POINTER: "fp32 tile GEMM, started through a function pointer: tests/test_small_coverage.py reads the two instantiations it can hold "
-                                    "from its initialiser and finds both in rows of small_ref.CASES"}
+# those rows beside streaming_ref's.
+BY_INT = re.compile(r"sgx_by_int<([^<>()]*)>\(")
 # Rows per entry point.  A row is a launch path someone decided to cover: dropping one has to be a decision made here too.
 ROWS = {"sgx_bias_act": 10, "sgx_lrelu_bwd": 7, "sgx_lrelu_bwd_bits": 3, "sgx_axpby": 11, "sgx_axpby_dev": 10, "sgx_blur3x3_act": 43, "sgx_blur3x3_bits": 8,
         "sgx_blur_kxk": 18, "sgx_pool2": 10, "sgx_up2": 10, "sgx_up2_add": 7, "sgx_downsample_fade_rgb": 3, "sgx_images_u8_to_nhwc": 8, "sgx_colsum": 16,
@@ -38,7 +37,28 @@ def launch_sites(path):
     with open(path) as f:
         src = f.read()
     src = re.sub(r"#define hipLaunchKernelGGL.*", "", src)
-    return [(m.group(1), (m.group(2) or "").strip()) for m in SITE.finditer(src)]
+    out = []
+    for m in SITE.finditer(src):
+        by = by_int_params(src, m.start())
+        out.append((m.group(1), (m.group(2) or "").strip()) + ((by,) if by else ()))
+    return out
+
+
+def by_int_params(src, at):
+    """The compile-time integers a site at src[at] may be instantiated with: {name: the listed values} for the parameter of the
+    sgx_by_int<a, b, ...>(j, [&](auto p) { constexpr int NAME = p(); ... }) call that encloses it (p() itself and every NAME it is given), read
+    from the text between the call and the site; {} where no such call is still open there."""
+    for b in reversed(list(BY_INT.finditer(src, 0, at))):
+        between = re.sub(r"//.*", "", src[b.end():at])
+        if between.count("(") - between.count(")") < 0:      # that call was closed before the site
+            continue
+        p = re.search(r"\(\s*auto\s+(\w+)\s*\)", between)
+        if not p:
+            return {}
+        values = [v.strip() for v in b.group(1).split(",")]
+        names = [p.group(1) + "()"] + re.findall(r"constexpr\s+int\s+(\w+)\s*=\s*" + p.group(1) + r"\(\)\s*;", between)
+        return {n: values for n in names}
+    return {}
 
 
 def split_args(targs):
@@ -57,12 +77,12 @@ def claims(site, kernel):
     return all(not LITERAL.match(s) or s == k for s, k in zip(sa, ka))
 
 
-def unclaimed(sites, cases, excluded, other=()):
+def unclaimed(sites, cases, excluded):
     kernels = {k for c in cases for k in c.kernels}
     miss = []
     for site in sites:
         text = site[0] + site[1]
-        if text in excluded or site[0] in other:
+        if text in excluded:
             continue
         mine = [k for k in kernels if claims(site, k)]
         if not mine:
@@ -73,6 +93,12 @@ def unclaimed(sites, cases, excluded, other=()):
             have = {split_args(re.match(r"^[A-Za-z_0-9]+(<.*>)$", k).group(1))[0] for k in mine}
             if not need <= have:
                 miss.append(f"{text} for {sorted(need - have)}")
+        for i, a in enumerate(split_args(site[1])):         # ... generic in the parameter of an enclosing sgx_by_int<a, b, ...>: every listed value
+            values = (site[2] if len(site) > 2 else {}).get(a)
+            if values:
+                have = {split_args(re.match(r"^[A-Za-z_0-9]+(<.*>)$", k).group(1))[i] for k in mine}
+                if not set(values) <= have:
+                    miss.append(f"{text} for {[int(v) for v in values if v not in have]}")
     return miss
 
 
@@ -82,16 +108,26 @@ def all_sites():
 
 def test_every_launch_site_is_claimed_or_excused():
     pw, sm = all_sites()
-    assert len(pw) == 52 and len(sm) == 28, (len(pw), len(sm))      # the scan found the launchers: every site of the two files
+    # the scan found the launchers: every site of the two files.  small.hip has one site per kernel: pixelnorm 2, mbstd 3 (<T>), the GEMM's
+    # outer-product, tile (<U> of sgx_by_int<1, 8>) and reduce kernels 3, the style affines 3 (<MB> of sgx_by_int<4, 8, 16, 32>), sumsq 2,
+    # the logistic head 1, scale_dev 1
+    assert len(pw) == 52 and len(sm) == 15, (len(pw), len(sm))
     assert unclaimed(pw, SR.CASES, SR.EXCLUDED_SITES) == []
-    assert unclaimed(sm, SR.CASES + SM.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) == []
-    assert unclaimed(sm, SR.CASES, SR.EXCLUDED_SITES, SMALL_HIP_OTHER) != []                    # ... a claim by the rows, no longer an excuse by name
+    assert unclaimed(sm, SR.CASES + SM.CASES, SR.EXCLUDED_SITES) == []
+    assert unclaimed(sm, SR.CASES, SR.EXCLUDED_SITES) != []                                     # ... a claim by the rows, no longer an excuse by name
+    # a site generic in an sgx_by_int parameter needs a row for each listed value: the lists are read, and dropping the rows of one value is noticed
+    by = {s[0]: s[2] for s in sm if len(s) > 2}
+    assert by == {"gemm_f32_kernel": {"u()": ["1", "8"], "U": ["1", "8"]},
+                  **{f"style_{e}_kernel": {"mb()": ["4", "8", "16", "32"], "MB": ["4", "8", "16", "32"]} for e in ("fwd", "bwd_data", "bwd_param")}}, by
+    no_k8 = [c for c in SM.CASES if SM.K8 not in c.kernels]
+    assert unclaimed(sm, SR.CASES + no_k8, SR.EXCLUDED_SITES) == ["gemm_f32_kernel<U> for [8]"]
+    no_mb16 = [c for c in SM.CASES if not (c.entry == "sgx_style_fwd" and SM.style_mb(c.args["B"]) == 16)]
+    assert unclaimed(sm, SR.CASES + no_mb16, SR.EXCLUDED_SITES) == ["style_fwd_kernel<MB> for [16]"]
     # the excuses name sites that exist, the covered small.hip kernels are there, and every reason is written down
     texts = {s[0] + s[1] for s in pw + sm}
     assert set(SR.EXCLUDED_SITES) <= texts, set(SR.EXCLUDED_SITES) - texts
-    assert set(SMALL_HIP_OTHER) <= {s[0] for s in sm}
     assert set(SR.SMALL_HIP_COVERED) <= {s[0] for s in sm}
-    assert all(len(r) > 10 for r in list(SR.EXCLUDED_SITES.values()) + list(SR.EXCLUDED_PATHS.values()) + list(SMALL_HIP_OTHER.values()))
+    assert all(len(r) > 10 for r in list(SR.EXCLUDED_SITES.values()) + list(SR.EXCLUDED_PATHS.values()))
     # and every kernel a row names is launched somewhere in the two files
     for c in SR.CASES:
         for k in c.kernels:
