@@ -418,10 +418,14 @@ int sgx_conv3x3_stats(const void* x, const void* w, void* y, const float* ebias,
  * channel that is 1 inside the image.  img, gi: fp32 [B][H][W][3];  w0: conv0.weight [C][C][3][3], s0 = its w_mul;  wr:
  * from_rgb.weight [C][3][1][1], sr = its w_mul;  br: from_rgb.bias (bscale = its b_mul) or NULL;  b0: conv0.bias * b_mul or NULL.
  * bf16 activations, C in {16, 32}, H % 16 == 0, W % 64 == 0 (sgx_rgbconv_ok); other shapes: sgx_rgb_in + sgx_conv3x3 + sgx_blur3x3_act.
- *   sgx_rgbconv_pack : wf [3][C][16] and wd [3][16][C] (activation dtype): the operand packs of the forward / image-gradient kernels.
+ *   sgx_rgbconv_pack : wf [3][C][16] (fp16 values in 2-byte elements: the forward kernels take fp16 operands) and wd [3][16][C] (bf16):
+ *                      the operand packs of the forward / image-gradient kernels.
  *   sgx_rgbconv_fwd  : epi 1: y = blur3x3(lrelu(conv(img) + b0)) and bits[pixel][C/8] = sign bits of the pre-activation (the
  *                      LeakyReLU-backward mask, as sgx_conv3x3_signbits writes them; may be NULL);  epi 0: y = conv(img) (no b0).
  *                      ones: 1 = with from_rgb's bias channel, 0 = without (the adjoint's own backward under R1's double backward).
+ *                      epi 0 (ones must be 0) scales every 16x64 tile by a power of two taken from the largest magnitude of the tile and
+ *                      its halo, so its accuracy is relative to that maximum at any magnitude from 2^-126 up; fp32-denormal inputs are
+ *                      outside the contract (a tile that holds nothing else is convolved unscaled and may come out as zeros).
  *   sgx_rgbconv_dgrad: gi = the gradient w.r.t. img given gz = the gradient w.r.t. the pre-activation (R1, models/Losses.py:197-211;
  *                      the generator step, models/GAN.py:640-655).
  *   sgx_rgbconv_wgrad: gradients of all four parameters from (img, gz) by the chain rule through the composition, written -- or, per

@@ -4,7 +4,9 @@ Kernel tests: integer-valued inputs (the gradient gz and the image in [-3, 3], W
 value, every product and every fp32 partial sum is an integer below 2^24 -- exact in ANY summation order -- and the kernels are
 compared with plain fp64 torch by exact equality: there is no tolerance to choose.  Each reference's magnitude is asserted to stay
 below 2^24 (and that of the intermediate dW', whose entries bound the partial sums of the chain rule).  Outputs live in
-``streaming_ref.Guarded`` buffers: sentinel fill, guard bands intact.
+``streaming_ref.Guarded`` buffers: sentinel fill, guard bands intact.  tests/test_gpu_rgbconv_paths.py runs the same shapes and more (rows of
+tests/rgbconv_ref.py, which restates these references at the C ABI's layouts and with non-unit scales; tests/test_rgbconv_coverage.py checks
+the two restatements against each other): single ``acc`` bits, NULL outputs, wfinish's second trip, the tile loop, the workspace itself.
 
 The D step: its final backward is asked for the parameters' gradients only (SGX_D_REAL_IMAGE_GRAD=0, the default), so the adjoint chain
 down to the real batch is not launched; the parameter gradients are those of the plain backward (=1) bit for bit."""

@@ -5,7 +5,11 @@ LeakyReLU -> BlurLayer (models/Blocks.py:137-142).  Every kernel against the fp6
 gradient, the four parameter gradients through the chain rule, the plain convolution of the double backward), and the whole
 discriminator -- scores, R1 image gradient, every parameter gradient of the logistic + R1 loss -- with the composed kernel ON
 against the same network with it OFF, both measured against the fp64 oracle.  bf16 storage: tolerances are those of one bf16
-rounding of the operands (2^-9 per element) plus the store, written next to each check."""
+rounding of the operands (2^-9 per element) plus the store, written next to each check.
+
+These are whole-tensor checks.  Every launch path of the same kernels -- the LDS-tile variants, the persistent loops, every row-block size,
+non-unit scales, NULL arguments -- is held per element, with the launch geometry, in tests/test_gpu_rgbconv_paths.py (rows and criteria:
+tests/rgbconv_ref.py; CPU side: tests/test_rgbconv_coverage.py)."""
 import numpy as np
 import pytest
 import torch
