@@ -326,6 +326,34 @@ int sgx_ada_update(const float* real_logits, int B, float* state, float target, 
 int sgx_diffaug_blit(const float* x, float* y, const float* u, int u_stride, const int* img_bits, int B, int H, int W, int policy_bits,
                      int adjoint, int with_bias, void* ws, size_t ws_bytes, void* stream);
 int sgx_ada_gates_n(const float* gu, int gu_stride, int n_ops, const float* state, int policy_bits, int* img_bits, int B, void* stream);
+/* The general geometric transformations, the second augmentation group of the ADA paper: policy_bits a subset of 32 = scale,
+ * 64 = rotate, 128 = aniso, applied in that order AFTER the ops above, composed per image into one affine map and applied by one
+ * bilinear resample of fp32 [B][H][W][3] images.  u: DEVICE fp32, row b at u + b * u_stride (u_stride >= 5), five uniforms in [0,1):
+ *   z_s = clamp(sqrt(-2 ln(1 - u0)) cos(2 pi u1), -3, 3);  s = 2^(0.2 z_s) when scale is on for the image, else 1
+ *   theta = 2 pi (u2 - 0.5) when rotate is on, else 0
+ *   z_a built like z_s from u3 and u4;  a = 2^(0.2 z_a) when aniso is on, else 1
+ *   T = Rot(theta) diag(s a, s / a),  Rot(theta) = [cos -sin; sin cos],  acting on (column, row) about the centre c = ((W-1)/2, (H-1)/2)
+ * (fp32, every product, quotient and difference rounded on its own; the precise logf / cosf / sinf / exp2f / sqrtf).  An op is on for
+ * an image when its bit is in policy_bits and either gu == NULL or its gate uniform is strictly below p = state[0] read on the device:
+ * gu row b at gu + b * gu_stride (gu_stride >= 3), columns 0..2 gating scale, rotate, aniso; gu and state are both given or both NULL.
+ * sgx_ada_geom_matrix: one launch writes mat[b][0..3] = T^-1 and mat[b][4..7] = T (row major) of every image, fp32 [B][8].  An image
+ *   whose three ops are all off gets exactly (1,0,0,1, 1,0,0,1): that row is the identity flag -- the resample copies such an image
+ *   bit for bit.  Made once per D evaluation; the forward, the adjoint and the R1 double backward read the table, never p.
+ * sgx_ada_geom: with s_p = c + T^-1 (p - c) for the pixel p = (column j, row i) and w(s, t) = max(0, 1 - |s_x - t_x|) max(0, 1 - |s_y - t_y|),
+ *   adjoint = 0:  y(p) = sum over the taps t = floor(s_p) + {0,1}^2 inside the image of w(s_p, t) x(t); taps outside contribute zero
+ *                 (the padding value of the integer translation), a pixel without a tap inside is +0;
+ *   adjoint = 1:  y(q) = sum over the pixels p of the image of w(s_p, q) x(p), as a gather: the candidates p are the integers of the
+ *                 bounding box of c + T (q - c + (-1,1)^2), at most 7 x 7 of them (the clamp of z at +-3 gives |T| entries <= 2.3).
+ *   s_p and w are computed as  s_x = c_x + (m0 d_x + m1 d_y),  s_y = c_y + (m2 d_x + m3 d_y),  d = p - c,  and as written above, every
+ *   product and sum rounded to fp32 on its own, by the same expression in both directions: the adjoint's coefficients are the forward's
+ *   bit for bit (as fp32 matrices the two are exact transposes), and a float32 restatement reproduces them exactly.  Accumulation is
+ *   acc += w * v, both roundings in fp32, taps in the order (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1), candidates row by row.
+ *   x != y, any H, W >= 1, no workspace, gathers only, no atomics: bit-reproducible.  With W % 4 == 0 and 16-byte aligned bases
+ *   a block resamples a 32 x 32 tile (and copies an identity image with 16-byte loads and stores).  Replaces the augment pipe's isotropic scale, arbitrary rotation and anisotropic scale (with bilinear
+ *   taps and zero padding instead of its band-limited filters and reflection padding). */
+int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
+                        void* stream);
+int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

@@ -356,7 +356,7 @@ class Discriminator(nn.Module):
                  ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
-        # 'color,xflip,rot90,translation,cutout' ('' = off); parsed here so that a bad policy fails at construction
+        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso' ('' = off); parsed here so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
         if self._diffaug_bits and num_channels != 3:
@@ -436,14 +436,43 @@ class Discriminator(nn.Module):
         if t is not None and tuple(t.shape) != (B, width):
             raise ValueError(f"{what} must be [{B},{width}] for this policy and batch, got {tuple(t.shape)}")
 
+    # the same two hooks for the geometric ops (scale, rotate, aniso): their [B,5] draws and, under ADA, their [B,3] gate uniforms
+    geom_override = None
+    geom_gate_override = None
+
     def _diffaug(self, img):
+        """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage."""
+        if self._diffaug_bits & F.DIFFAUG_PIXEL_MASK:
+            img = self._diffaug_pixel(img, self._diffaug_bits & F.DIFFAUG_PIXEL_MASK)
+        if self._diffaug_bits & F.DIFFAUG_GEOM_MASK:
+            img = self._diffaug_geom(img)
+        return img
+
+    def _diffaug_geom(self, img):
+        """scale, rotate, aniso: one draw of its own per D evaluation ([B,5]; [B,8] under ADA, columns 5..7 the gates), turned into the
+        per-image table ONCE, here; the resample, its adjoint and the R1 double backward of this evaluation read the table, never p."""
+        B = img.shape[0]
+        u, gu = self.geom_override, self.geom_gate_override
+        self._override_ok(u, B, 5, "geom_override")
+        if not self.ada:
+            if u is None:
+                u = torch.rand(B, 5, device=img.device)
+            return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits))
+        self._override_ok(gu, B, 3, "geom_gate_override")
+        if u is None or gu is None:
+            r = torch.rand(B, 8, device=img.device)
+            u = r[:, :5] if u is None else u
+            gu = r[:, 5:] if gu is None else gu
+        return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits, gu, self.ada_state))
+
+    def _diffaug_pixel(self, img, bits):
         u = self.diffaug_override
-        if self._diffaug_bits & F.DIFFAUG_BLIT_BITS:
-            return self._diffaug_blit(img, u)
+        if bits & F.DIFFAUG_BLIT_BITS:
+            return self._diffaug_blit(img, u, bits)
         if not self.ada:
             if u is None:
                 u = torch.rand(img.shape[0], 7, device=img.device)       # torch's graph-safe generator: fresh draws at every replay
-            return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+            return F.call(F.DiffAugFn, img, u, bits)
         # ADA: one draw per D evaluation, columns 0..6 the ops' parameters and 7..9 their gates.  The gates are turned into per-image
         # bits ONCE, here; the adjoint, the linear part and the R1 double backward of this evaluation read the bits, never p.
         gu = self.ada_gate_override
@@ -451,23 +480,23 @@ class Discriminator(nn.Module):
             r = torch.rand(img.shape[0], 10, device=img.device)
             u = r[:, :7].contiguous() if u is None else u                 # (saved for the backward passes: contiguous once)
             gu = r[:, 7:] if gu is None else gu
-        return F.call(F.DiffAugFn, img, u, self._diffaug_bits, F.ada_gates(gu, self.ada_state, self._diffaug_bits))
+        return F.call(F.DiffAugFn, img, u, bits, F.ada_gates(gu, self.ada_state, bits))
 
-    def _diffaug_blit(self, img, u):
+    def _diffaug_blit(self, img, u, bits):
         """A policy with xflip or rot90: nine draws per image, five gates; the kernels read rows of the one [B,14] draw in place."""
         B = img.shape[0]
         self._override_ok(u, B, 9, "diffaug_override")
         if not self.ada:
             if u is None:
                 u = torch.rand(B, 9, device=img.device)
-            return F.call(F.DiffAugFn, img, u, self._diffaug_bits)
+            return F.call(F.DiffAugFn, img, u, bits)
         gu = self.ada_gate_override
         self._override_ok(gu, B, 5, "ada_gate_override")
         if u is None or gu is None:
             r = torch.rand(B, 14, device=img.device)
             u = r[:, :9] if u is None else u
             gu = r[:, 9:] if gu is None else gu
-        return F.call(F.DiffAugFn, img, u, self._diffaug_bits, F.ada_gates_n(gu, self.ada_state, self._diffaug_bits))
+        return F.call(F.DiffAugFn, img, u, bits, F.ada_gates_n(gu, self.ada_state, bits))
 
     @property
     def ada_p(self):
@@ -975,7 +1004,9 @@ class StyleGAN:
                self.dis._diffaug_bits, self.dis.training,              # ... and whether (and from where) D's input is augmented
                None if self.dis.diffaug_override is None else self.dis.diffaug_override.data_ptr(),
                (self.dis.ada_target, self.dis.ada_interval, self.dis.ada_kimg) if self._ada_on() else None,   # ... baked into the update launch
-               None if not self._ada_on() or self.dis.ada_gate_override is None else self.dis.ada_gate_override.data_ptr())
+               None if not self._ada_on() or self.dis.ada_gate_override is None else self.dis.ada_gate_override.data_ptr(),
+               None if self.dis.geom_override is None else self.dis.geom_override.data_ptr(),
+               None if not self._ada_on() or self.dis.geom_gate_override is None else self.dis.geom_gate_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)

@@ -1,0 +1,246 @@
+// The general geometric group of the ADA paper (Karras et al., NeurIPS 2020) on the discriminator's fp32 RGB input: isotropic scale,
+// arbitrary rotation and anisotropic scale of one image composed into ONE affine map T about the image centre, applied by a single
+// bilinear resample (definitions in include/sgx.h):
+//   y(p) = sum_t w(s_p, t) x(t)        forward: the four taps t = floor(s_p) + {0,1}^2 inside the image, s_p = c + T^-1 (p - c)
+//   z(q) = sum_p w(s_p, q) g(p)        adjoint: the output pixels p whose taps include q, found from the bounding box of T(q + (-1,1)^2)
+// Both are gathers (no atomics: bit-reproducible), and both compute the position s_p and the weight w with the SAME expression
+// (geom_pos, geom_w: every product and sum rounded to fp32 on its own), so the adjoint's coefficients are the forward's bit for bit.
+// sgx_ada_geom_matrix turns one D evaluation's draws (and, under ADA, its gate uniforms against p) into the per-image table
+// {T^-1, T} once; the forward, the adjoint and the R1 double backward read the table, never p.  An image with its three ops off gets
+// the exact identity row, which IS its flag: both resample kernels copy such an image (a block-uniform branch).
+#include "common.h"
+
+enum { DG_SCALE = 32, DG_ROTATE = 64, DG_ANISO = 128, DG_OPS = DG_SCALE | DG_ROTATE | DG_ANISO };
+constexpr int DG_BLOCK = 256;
+constexpr float DG_MARGIN = 0.03125f;               // slack of the adjoint's candidate box, in pixels (covers T T^-1 != I in fp32)
+
+typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));   // one 12-byte pixel at a 4-byte aligned address (dwordx3)
+
+// z = clamp(sqrt(-2 ln(1 - ua)) cos(2 pi ub), -3, 3);  2^(0.2 z)
+__device__ __forceinline__ float dg_lognormal(float ua, float ub) {
+    const float r = sqrtf(__fmul_rn(-2.f, logf(__fsub_rn(1.f, ua))));
+    const float z = __fmul_rn(r, cosf(__fmul_rn(6.283185307179586f, ub)));
+    return exp2f(__fmul_rn(0.2f, fminf(fmaxf(z, -3.f), 3.f)));
+}
+
+__global__ __launch_bounds__(DG_BLOCK) void ada_geom_matrix_kernel(const float* __restrict__ u, int u_stride, const float* __restrict__ gu,
+                                                                   int gu_stride, const float* __restrict__ state, int policy,
+                                                                   float* __restrict__ mat, int B) {
+    const int b = blockIdx.x * DG_BLOCK + threadIdx.x;
+    if (b >= B) return;
+    int on = policy;
+    if (gu) {
+        const float p = state[0];
+        const float* g = gu + (size_t)gu_stride * b;
+        on &= (g[0] < p ? DG_SCALE : 0) | (g[1] < p ? DG_ROTATE : 0) | (g[2] < p ? DG_ANISO : 0);
+    }
+    float* m = mat + 8 * (size_t)b;
+    if (!(on & DG_OPS)) {                                        // the identity row: what the resample kernels copy under
+        m[0] = 1.f; m[1] = 0.f; m[2] = 0.f; m[3] = 1.f; m[4] = 1.f; m[5] = 0.f; m[6] = 0.f; m[7] = 1.f;
+        return;
+    }
+    const float* ub = u + (size_t)u_stride * b;
+    const float s = (on & DG_SCALE) ? dg_lognormal(ub[0], ub[1]) : 1.f;
+    const float th = (on & DG_ROTATE) ? __fmul_rn(6.283185307179586f, __fsub_rn(ub[2], 0.5f)) : 0.f;
+    const float a = (on & DG_ANISO) ? dg_lognormal(ub[3], ub[4]) : 1.f;
+    const float sx = __fmul_rn(s, a), sy = __fdiv_rn(s, a);
+    const float c = cosf(th), sn = sinf(th);
+    // T = Rot(th) diag(sx, sy) on (column, row);  T^-1 = diag(1/sx, 1/sy) Rot(-th)
+    m[0] = __fdiv_rn(c, sx); m[1] = __fdiv_rn(sn, sx); m[2] = __fdiv_rn(-sn, sy); m[3] = __fdiv_rn(c, sy);
+    m[4] = __fmul_rn(c, sx); m[5] = __fmul_rn(-sn, sy); m[6] = __fmul_rn(sn, sx); m[7] = __fmul_rn(c, sy);
+}
+
+struct DgMat { float i00, i01, i10, i11, t00, t01, t10, t11; };
+
+__device__ __forceinline__ DgMat dg_load_mat(const float* __restrict__ m) {
+    DgMat q;
+    q.i00 = m[0]; q.i01 = m[1]; q.i10 = m[2]; q.i11 = m[3]; q.t00 = m[4]; q.t01 = m[5]; q.t10 = m[6]; q.t11 = m[7];
+    return q;
+}
+
+__device__ __forceinline__ bool dg_identity(const DgMat& q) {
+    return q.i00 == 1.f && q.i01 == 0.f && q.i10 == 0.f && q.i11 == 1.f && q.t00 == 1.f && q.t01 == 0.f && q.t10 == 0.f && q.t11 == 1.f;
+}
+
+// s_p = c + T^-1 (p - c) for the output pixel p = (column j, row i): THE position expression of the forward and the adjoint.
+__device__ __forceinline__ void geom_pos(const DgMat& q, float cx, float cy, int i, int j, float& sx, float& sy) {
+    const float dx = __fsub_rn((float)j, cx), dy = __fsub_rn((float)i, cy);
+    sx = __fadd_rn(cx, __fadd_rn(__fmul_rn(q.i00, dx), __fmul_rn(q.i01, dy)));
+    sy = __fadd_rn(cy, __fadd_rn(__fmul_rn(q.i10, dx), __fmul_rn(q.i11, dy)));
+}
+
+// w(s, t) = max(0, 1 - |s_x - t_x|) max(0, 1 - |s_y - t_y|): THE weight expression of the forward and the adjoint.
+__device__ __forceinline__ float geom_w(float sx, float sy, int tx, int ty) {
+    const float wx = fmaxf(0.f, __fsub_rn(1.f, fabsf(__fsub_rn(sx, (float)tx))));
+    const float wy = fmaxf(0.f, __fsub_rn(1.f, fabsf(__fsub_rn(sy, (float)ty))));
+    return __fmul_rn(wx, wy);
+}
+
+__device__ __forceinline__ void dg_acc(float (&acc)[3], float w, const float* __restrict__ px) {
+    const f32x3u v = *reinterpret_cast<const f32x3u*>(px);
+    acc[0] = __fadd_rn(acc[0], __fmul_rn(w, v.x));
+    acc[1] = __fadd_rn(acc[1], __fmul_rn(w, v.y));
+    acc[2] = __fadd_rn(acc[2], __fmul_rn(w, v.z));
+}
+
+// Forward value of output pixel (i, j): taps in the order (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1), those outside the image
+// skipped.  A position far outside (|s| beyond the int range cannot occur: |T^-1| <= 2.3 and the image is < 2^31 / 3 floats).
+__device__ __forceinline__ void dg_fwd_px(const float* __restrict__ xb, int H, int W, const DgMat& q, float cx, float cy, int i, int j,
+                                          float (&acc)[3]) {
+    float sx, sy;
+    geom_pos(q, cx, cy, i, j, sx, sy);
+    acc[0] = acc[1] = acc[2] = 0.f;
+    if (!(sx > -1.f && sx < (float)W && sy > -1.f && sy < (float)H)) return;     // no tap inside (also: NaN positions of a bad table)
+    const int x0 = (int)floorf(sx), y0 = (int)floorf(sy);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const int tx = x0 + dx, ty = y0 + dy;
+            if (tx >= 0 && tx < W && ty >= 0 && ty < H) dg_acc(acc, geom_w(sx, sy, tx, ty), xb + ((size_t)ty * W + tx) * 3);
+        }
+    }
+}
+
+// Adjoint value of pixel q = (row qi, column qj): the candidates p are the integers of the box centre +- (extent + margin), centre
+// = c + T (q - c), extent = (|t00| + |t01|, |t10| + |t11|); nx, ny (the trip counts) come from the matrix alone.  Candidates are
+// visited row by row, those with a zero weight or outside the image skipped.
+__device__ __forceinline__ void dg_adj_px(const float* __restrict__ gb, int H, int W, const DgMat& q, float cx, float cy, float ex, float ey,
+                                          int nx, int ny, int qi, int qj, float (&acc)[3]) {
+    const float dx = (float)qj - cx, dy = (float)qi - cy;
+    const float px = cx + (q.t00 * dx + q.t01 * dy), py = cy + (q.t10 * dx + q.t11 * dy);
+    acc[0] = acc[1] = acc[2] = 0.f;
+    if (!(px > -8.f && px < (float)W + 8.f && py > -8.f && py < (float)H + 8.f)) return;      // the whole box is outside
+    const int j0 = (int)ceilf(px - ex), i0 = (int)ceilf(py - ey);
+    for (int di = 0; di < ny; ++di) {
+        const int i = i0 + di;
+        if (i < 0 || i >= H) continue;
+        for (int dj = 0; dj < nx; ++dj) {
+            const int j = j0 + dj;
+            if (j < 0 || j >= W) continue;
+            float sx, sy;
+            geom_pos(q, cx, cy, i, j, sx, sy);
+            const float w = geom_w(sx, sy, qj, qi);
+            if (w > 0.f) dg_acc(acc, w, gb + ((size_t)i * W + j) * 3);
+        }
+    }
+}
+
+struct DgBox { float ex, ey; int nx, ny; };                     // the adjoint's candidate box: half extents (with the slack) and trip counts
+
+template <bool ADJ>
+__device__ __forceinline__ DgBox dg_box(const DgMat& q) {
+    DgBox bx = {0.f, 0.f, 0, 0};
+    if (ADJ) {
+        bx.ex = fabsf(q.t00) + fabsf(q.t01) + DG_MARGIN; bx.ey = fabsf(q.t10) + fabsf(q.t11) + DG_MARGIN;
+        bx.nx = min((int)floorf(2.f * bx.ex) + 1, 7); bx.ny = min((int)floorf(2.f * bx.ey) + 1, 7);
+    }
+    return bx;
+}
+
+// Any H, W, any 4-byte aligned base: one pixel per thread in row order, one trip (short-lived blocks).  grid (ceil(H W / DG_BLOCK), B).
+template <bool ADJ>
+__global__ __launch_bounds__(DG_BLOCK) void ada_geom_px_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ mat,
+                                                               int H, int W) {
+    const int b = blockIdx.y;
+    const DgMat q = dg_load_mat(mat + 8 * (size_t)b);
+    const int unit = blockIdx.x * DG_BLOCK + threadIdx.x;
+    if (unit >= H * W) return;
+    const int i = unit / W, j = unit - i * W;
+    const size_t at = ((size_t)b * H * W + unit) * 3;
+    float acc[3];
+    if (dg_identity(q)) {                                        // (block-uniform) a copy, bit for bit
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k] = x[at + k];
+    } else {
+        const float* xb = x + (size_t)b * H * W * 3;
+        const float cx = (float)(W - 1) * 0.5f, cy = (float)(H - 1) * 0.5f;
+        const DgBox bx = dg_box<ADJ>(q);
+        if (ADJ) dg_adj_px(xb, H, W, q, cx, cy, bx.ex, bx.ey, bx.nx, bx.ny, i, j, acc);
+        else dg_fwd_px(xb, H, W, q, cx, cy, i, j, acc);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) y[at + k] = acc[k];
+}
+
+// W % 4 == 0, 16-byte aligned bases.  A block owns a DG_TILE x DG_TILE output tile of one image, a wave eight rows of it, and in each
+// of its four trips the wave's lanes are an 8 x 8 patch of pixels (lane = 8 row + column).  An affine map takes the patch to a small
+// parallelogram of the source, so the 64 addresses of one tap load fall on a dozen cache lines; with the lanes of a wave laid along a
+// row instead (the first version: four consecutive pixels per lane) a turned image spread them over 64 lines, and the launch cost 6 to
+// 11 times the blit tile kernel's.  An identity image is copied in row order, four pixels (three 16-byte loads
+// and stores) per thread: the grid's DG_TILE^2-pixel tiles are at least as many as its DG_TILE^2-pixel runs.
+// grid (ceil(H / DG_TILE) * ceil(W / DG_TILE), B).
+constexpr int DG_TILE = 32;
+static_assert(DG_TILE * DG_TILE == 4 * DG_BLOCK && DG_TILE == 4 * 8 && DG_BLOCK == 4 * WAVE, "four waves of eight rows, four 8 x 8 patches each");
+
+template <bool ADJ>
+__global__ __launch_bounds__(DG_BLOCK) void ada_geom_tile_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ mat,
+                                                                 int H, int W, int tiles_x) {
+    const int b = blockIdx.y;
+    const DgMat q = dg_load_mat(mat + 8 * (size_t)b);
+    const float* xb = x + (size_t)b * H * W * 3;
+    float* yb = y + (size_t)b * H * W * 3;
+    if (dg_identity(q)) {                                        // (block-uniform) a copy, bit for bit
+        const int unit = blockIdx.x * DG_BLOCK + threadIdx.x;
+        if (unit >= H * (W / 4)) return;
+        const float4* s = reinterpret_cast<const float4*>(xb + (size_t)unit * 12);
+        const float4 v0 = s[0], v1 = s[1], v2 = s[2];
+        float4* d = reinterpret_cast<float4*>(yb + (size_t)unit * 12);
+        d[0] = v0; d[1] = v1; d[2] = v2;
+        return;
+    }
+    const int ti = blockIdx.x / tiles_x, tj = blockIdx.x - ti * tiles_x;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int i = ti * DG_TILE + (threadIdx.x / WAVE) * 8 + (lane >> 3);
+    if (i >= H) return;
+    const float cx = (float)(W - 1) * 0.5f, cy = (float)(H - 1) * 0.5f;
+    const DgBox bx = dg_box<ADJ>(q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = tj * DG_TILE + 8 * k + (lane & 7);
+        if (j >= W) continue;
+        float acc[3];
+        if (ADJ) dg_adj_px(xb, H, W, q, cx, cy, bx.ex, bx.ey, bx.nx, bx.ny, i, j, acc);
+        else dg_fwd_px(xb, H, W, q, cx, cy, i, j, acc);
+        f32x3u v; v.x = acc[0]; v.y = acc[1]; v.z = acc[2];
+        *reinterpret_cast<f32x3u*>(yb + ((size_t)i * W + j) * 3) = v;
+    }
+}
+
+extern "C" int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat,
+                                   int B, void* stream) {
+    SGX_REQUIRE(u && mat && B > 0, SGX_EINVAL, "ada_geom_matrix: bad arguments (B=%d)", B);
+    SGX_REQUIRE(u_stride >= 5, SGX_EINVAL, "ada_geom_matrix: draws %d floats apart, need at least 5", u_stride);
+    SGX_REQUIRE((gu == nullptr) == (state == nullptr), SGX_EINVAL, "ada_geom_matrix: gate uniforms and the ADA state come together or not at all");
+    SGX_REQUIRE(!gu || gu_stride >= 3, SGX_EINVAL, "ada_geom_matrix: gate uniforms %d floats apart, need at least 3", gu_stride);
+    SGX_REQUIRE(policy_bits >= 0 && (policy_bits & ~DG_OPS) == 0, SGX_EINVAL, "ada_geom_matrix: policy bits %d (scale 32, rotate 64, aniso 128)",
+                policy_bits);
+    SGX_NOTE(0.0, (20.0 + (gu ? 16.0 : 0.0) + 32.0) * B, "ada_geom_matrix B%d", B);
+    hipLaunchKernelGGL(ada_geom_matrix_kernel, dim3((B + DG_BLOCK - 1) / DG_BLOCK), dim3(DG_BLOCK), 0, (hipStream_t)stream, u, u_stride, gu, gu_stride,
+                       state, policy_bits, mat, B);
+    SGX_LAUNCH_CHECK("ada_geom_matrix");
+    return 0;
+}
+
+extern "C" int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream) {
+    SGX_REQUIRE(x && y && mat && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "ada_geom: bad arguments (B=%d %dx%d)", B, H, W);
+    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "ada_geom: image of %dx%d too large", H, W);
+    SGX_REQUIRE(x != y, SGX_EINVAL, "ada_geom: in place is not supported (the passes gather)");
+    hipStream_t st = (hipStream_t)stream;
+    const char* dir = adjoint ? "adj" : "fwd";
+    // the tile path where an identity image can be copied in 16-byte pieces (rows of whole groups of four, 16-byte aligned bases)
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    if (vec) {
+        const int tiles_x = (W + DG_TILE - 1) / DG_TILE, tiles_y = (H + DG_TILE - 1) / DG_TILE;
+        SGX_NOTE(0.0, 24.0 * B * H * W, "ada_geom_tile B%d %dx%d %s", B, H, W, dir);
+        if (adjoint) hipLaunchKernelGGL((ada_geom_tile_kernel<true>), dim3(tiles_x * tiles_y, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W, tiles_x);
+        else hipLaunchKernelGGL((ada_geom_tile_kernel<false>), dim3(tiles_x * tiles_y, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W, tiles_x);
+    } else {
+        const unsigned gx = (unsigned)(((size_t)H * W + DG_BLOCK - 1) / DG_BLOCK);
+        SGX_NOTE(0.0, 24.0 * B * H * W, "ada_geom_px B%d %dx%d %s", B, H, W, dir);
+        if (adjoint) hipLaunchKernelGGL((ada_geom_px_kernel<true>), dim3(gx, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W);
+        else hipLaunchKernelGGL((ada_geom_px_kernel<false>), dim3(gx, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W);
+    }
+    SGX_LAUNCH_CHECK("ada_geom");
+    return 0;
+}

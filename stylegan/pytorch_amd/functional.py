@@ -2433,23 +2433,29 @@ def nchw_view(x_nhwc):
 DIFFAUG_OPS = ("color", "xflip", "rot90", "translation", "cutout")          # the canonical order: the order the ops are applied in
 DIFFAUG_BITS = {"color": 1, "translation": 2, "cutout": 4, "xflip": 8, "rot90": 16}    # the kernels' policy bits (not the op's index)
 DIFFAUG_BLIT_BITS = DIFFAUG_BITS["xflip"] | DIFFAUG_BITS["rot90"]
+# the general geometric group of the ADA paper, applied after the five ops above by its own kernels (``sgx_ada_geom``, further down)
+DIFFAUG_GEOM_OPS = ("scale", "rotate", "aniso")
+DIFFAUG_GEOM_BITS = {"scale": 32, "rotate": 64, "aniso": 128}
+DIFFAUG_GEOM_MASK = 32 | 64 | 128
+DIFFAUG_PIXEL_MASK = 31                                                      # the bits the DiffAugment / blitting entry points take
 
 
 def diffaug_policy_bits(policy):
-    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout`` in that
-    (canonical) order, each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
+    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout,scale,rotate,aniso``
+    in that (canonical) order, each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
     if policy is None:
         return 0
     if not isinstance(policy, str):
         raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
+    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS
     bits, last = 0, -1
     for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
-        if name not in DIFFAUG_OPS:
-            raise ValueError(f"unknown DiffAugment op {name!r} in {policy!r} (known: {','.join(DIFFAUG_OPS)})")
-        k = DIFFAUG_OPS.index(name)
+        if name not in order:
+            raise ValueError(f"unknown DiffAugment op {name!r} in {policy!r} (known: {','.join(order)})")
+        k = order.index(name)
         if k <= last:
-            raise ValueError(f"DiffAugment policy {policy!r}: ops must appear once each, in the order {','.join(DIFFAUG_OPS)}")
-        bits |= DIFFAUG_BITS[name]
+            raise ValueError(f"DiffAugment policy {policy!r}: ops must appear once each, in the order {','.join(order)}")
+        bits |= DIFFAUG_BITS[name] if name in DIFFAUG_BITS else DIFFAUG_GEOM_BITS[name]
         last = k
     return bits
 
@@ -2583,3 +2589,76 @@ def ada_update(real_logits, state, target, adjust_per_image, interval):
     N.check(N.lib().sgx_ada_update(N.ptr(lg), lg.numel(), N.ptr(state), float(target), float(adjust_per_image), int(interval), N.stream()),
             "sgx_ada_update")
     return state
+
+
+# The general geometric group of the ADA paper (scale, rotate, aniso; ``sgx_ada_geom_matrix`` / ``sgx_ada_geom``, include/sgx.h): one
+# table of per-image affine maps per D evaluation and one bilinear resample R.  R is linear, so AdaGeomFn (R x) and AdaGeomAdjFn (R^T g)
+# are each other's backward: the pair closes under differentiation and the R1 double backward runs through it.  Both save only the table.
+def ada_geom_matrix(u, bits, gu=None, state=None):
+    """u fp32 [B,5] draws (rows of a wider draw are read in place) -> the fp32 [B,8] table {T^-1, T} of the geometric ops in ``bits``
+    (32 scale, 64 rotate, 128 aniso); with ``gu`` fp32 [B,3] gate uniforms and the ADA ``state``, an op is on for image b iff
+    gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0,1, 1,0,0,1)."""
+    if u.dim() != 2 or u.shape[1] != 5 or u.dtype != torch.float32:
+        raise N.SgxError(f"ada_geom_matrix: need fp32 [B,5] draws, got {tuple(u.shape)} {u.dtype}")
+    if u.stride(1) != 1 or u.stride(0) < 5:
+        u = _c(u)
+    if (gu is None) != (state is None):
+        raise N.SgxError("ada_geom_matrix: gate uniforms and the ADA state come together or not at all")
+    B = u.shape[0]
+    gp, gs = None, 0
+    if gu is not None:
+        if tuple(gu.shape) != (B, 3) or gu.dtype != torch.float32 or gu.device != u.device:
+            raise N.SgxError(f"ada_geom_matrix: need fp32 [{B},3] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
+        if gu.stride(1) != 1 or gu.stride(0) < 3:
+            gu = _c(gu)
+        _ada_state_ok(state, u.device, "ada_geom_matrix")
+        gp, gs = gu.data_ptr(), gu.stride(0)
+    if not u.is_cuda:
+        raise N.SgxError("libsgx_hip kernels need GPU tensors (no CPU fallback exists for this path)")
+    mat =torch.empty(B, 8, dtype=torch.float32, device=u.device)
+    N.check(N.lib().sgx_ada_geom_matrix(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_GEOM_MASK, N.ptr(mat), B,
+                                        N.stream()), "sgx_ada_geom_matrix")
+    return mat
+
+
+def _ada_geom(x, mat, adjoint):
+    x = _c(x)
+    if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
+        raise N.SgxError(f"ada_geom: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    B, H, W, _ = x.shape
+    if tuple(mat.shape) != (B, 8) or mat.dtype != torch.float32 or mat.device != x.device:
+        raise N.SgxError(f"ada_geom: need an fp32 [{B},8] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
+    y = torch.empty_like(x)
+    N.check(N.lib().sgx_ada_geom(N.ptr(x), N.ptr(y), N.ptr(_c(mat)), B, H, W, int(adjoint), N.stream()), "sgx_ada_geom")
+    return y
+
+
+class AdaGeomFn(Function):
+    """y = R x, the bilinear resample under the table ``mat`` (no gradient); backward = the adjoint (AdaGeomAdjFn), none when x needs
+    no gradient (the D step's fakes)."""
+
+    @staticmethod
+    def forward(ctx, x, mat):
+        ctx.save_for_backward(mat)
+        return _ada_geom(x, mat, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        mat, = ctx.saved_tensors
+        return _bcall(AdaGeomAdjFn, g, mat), None
+
+
+class AdaGeomAdjFn(Function):
+    """z = R^T g; backward = R (AdaGeomFn)."""
+
+    @staticmethod
+    def forward(ctx, g, mat):
+        ctx.save_for_backward(mat)
+        return _ada_geom(g, mat, True)
+
+    @staticmethod
+    def backward(ctx, gg):
+        mat, = ctx.saved_tensors
+        return _bcall(AdaGeomFn, gg, mat), None
