@@ -470,6 +470,24 @@ int sgx_rgbconv_fwd(const float* img, const void* wf, const float* b0, void* y, 
  * ablations of the row-streaming kernel (4 no output stores, 8 no sign bits -- wrong results by design), 0 = none. */
 int sgx_rgbconv_tune(int fwd_variant, int nit, int dbg);
 int sgx_rgbconv_dgrad(const void* gz, const void* wd, float* gi, int B, int H, int W, int C, int dtype, void* stream);
+/* Host-only query: what sgx_rgbconv_pack / _fwd / _dgrad / _wgrad (entry SGX_RGBCONV_PLAN_PACK / _FWD / _DGRAD / _WGRAD) will launch for
+ * this shape of bf16 activations under the current sgx_rgbconv_tune state.  The entry points execute the same plan.  B, H, W are not
+ * read for the pack, epi only for the forward.  out[SGX_RGBCONV_PLAN_INTS]:
+ *   [0]  the kernel: 0 rgbconv_pack_kernel, 1 rgbconv_fwd_kernel<[1], [2]> (the LDS-tile forward: epi 0, or variant 1 / 2),
+ *        2 rgbconv_fwdblur_kernel<[1]> (epi 1, variant 0), 3 rgbconv_dgrad_kernel<[1]>,
+ *        4 rgbconv_wgrad_kernel<[1]>, followed by rgbconv_wfinish_kernel and rgbconv_chain_kernel
+ *   [1]  CB = C / 16;  [2] EPI: the forward's epi, 0 for the other entries
+ *   [3]  that kernel's grid (256-thread blocks; wgrad: the number of block partials in the workspace);  [4] its dynamic LDS in bytes
+ *   [5..7]  its geometry arguments: strips of 14 columns per row, row blocks per image, six-row steps per row block (fwdblur);  strips,
+ *        row blocks of 32 rows, 0 (dgrad);  tiles per row, tile rows per image, tiles in all (the LDS-tile forward, wgrad);  0 (pack)
+ *   [8]  the grid of rgbconv_wfinish_kernel, [9] of rgbconv_chain_kernel (wgrad; else 0)
+ *   [10] the resident blocks per CU a persistent grid was sized with, [3] = ceil8(min([7], [10] * compute units)): the occupancy
+ *        the runtime reports for rgbconv_fwd_kernel (1..4; 1 where there is no device), 3 for wgrad; 0 for a grid that is not persistent
+ * Returns 0; SGX_EUNSUPPORTED for a shape sgx_rgbconv_ok refuses (the pack: C other than 16 or 32); SGX_EINVAL for an unknown entry,
+ * an epi other than 0 or 1, or a NULL out.  out is zeroed on every error but the last. */
+enum { SGX_RGBCONV_PLAN_PACK = 0, SGX_RGBCONV_PLAN_FWD = 1, SGX_RGBCONV_PLAN_DGRAD = 2, SGX_RGBCONV_PLAN_WGRAD = 3 };
+#define SGX_RGBCONV_PLAN_INTS 11
+int sgx_rgbconv_plan(int entry, int B, int H, int W, int C, int epi, int* out);
 size_t sgx_rgbconv_wgrad_ws_bytes(int B, int H, int W, int C);
 int sgx_rgbconv_wgrad(const float* img, const void* gz, int ones, const float* w0, float s0, const float* wr, float sr, const float* br,
                       float bscale, float* dw0, float* db0, float* dwr, float* dbr, int acc, void* ws, size_t ws_bytes, int B, int H, int W,

@@ -104,6 +104,19 @@ static __device__ __forceinline__ RcSched rc_sched(int ntiles) {
     return s;
 }
 struct rgb3 { float r, g, b; };                            // 12 bytes, 4-byte aligned: one global_load_dwordx3
+// tile t of the [B][tiles_y][tiles_x] raster of TH x TW tiles: its image and its first row and column
+template <int TH, int TW>
+static __device__ __forceinline__ void rc_tile_at(int t, int tiles_x, int tiles_y, int& b, int& ty0, int& tx0) {
+    const int tx = t % tiles_x; t /= tiles_x;
+    const int ty = t % tiles_y;
+    b = t / tiles_y; ty0 = ty * TH; tx0 = tx * TW;
+}
+// four 16-bit values in two words -> an MFMA operand fragment
+static __device__ __forceinline__ s16x4 rc_frag(unsigned lo, unsigned hi) {
+    s16x4 f;
+    f[0] = (short)(lo & 0xffffu); f[1] = (short)(lo >> 16); f[2] = (short)(hi & 0xffffu); f[3] = (short)(hi >> 16);
+    return f;
+}
 
 template <int CB, int EPI>
 __global__ __launch_bounds__(256) void rgbconv_fwd_kernel(const float* __restrict__ img, const bf16_t* __restrict__ wf, const float* __restrict__ b0,
@@ -132,14 +145,9 @@ __global__ __launch_bounds__(256) void rgbconv_fwd_kernel(const float* __restric
     constexpr int NIT = (IPX + 255) / 256;
     rgb3 pv[NIT];
     unsigned okm = 0;
-    auto tile_at = [&](int t, int& b, int& ty0, int& tx0) {
-        const int tx = t % tiles_x; t /= tiles_x;
-        const int ty = t % tiles_y;
-        b = t / tiles_y; ty0 = ty * TH; tx0 = tx * TW;
-    };
     auto load_tile = [&](int t) {
         int b, ty0, tx0;
-        tile_at(t, b, ty0, tx0);
+        rc_tile_at<TH, TW>(t, tiles_x, tiles_y, b, ty0, tx0);
         okm = 0;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(256) void rgbconv_fwd_kernel(const float* __restric
     load_tile(sc.first);
     for (int t = sc.first; t < sc.end; t += sc.stride) {
         int b, ty0, tx0;
-        tile_at(t, b, ty0, tx0);
+        rc_tile_at<TH, TW>(t, tiles_x, tiles_y, b, ty0, tx0);
         // EPI 0 (the plain convolution: the adjoint's own backward under the R1 double backward) is fed a GRADIENT, not an image:
         // gamma / B * dD/dimg per pixel is 1e-6..1e-5 at 1024^2, below fp16's normal range (6.1e-5).  The operation is linear, so the
         // tile is brought into fp16 range by a power of two taken from its own largest magnitude (exact), and the accumulators
@@ -199,8 +207,7 @@ __global__ __launch_bounds__(256) void rgbconv_fwd_kernel(const float* __restric
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
                 const uint2 raw = imgl[(zr + ky) * IW + zc + l4];
-                s16x4 bf;
-                bf[0] = (short)(raw.x & 0xffffu); bf[1] = (short)(raw.x >> 16); bf[2] = (short)(raw.y & 0xffffu); bf[3] = (short)(raw.y >> 16);
+                const s16x4 bf = rc_frag(raw.x, raw.y);
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) acc[cb] = mma16h(wfr[cb][ky], bf, acc[cb]);
             }
@@ -346,9 +353,7 @@ static __device__ __forceinline__ void fwdblur_walk(const float* __restrict__ ib
             const unsigned m = (unsigned)gy < (unsigned)H ? lmask : 0u;
             p01 &= m; p23 &= m;
         }
-        s16x4 f;
-        f[0] = (short)(p01 & 0xffffu); f[1] = (short)(p01 >> 16); f[2] = (short)(p23 & 0xffffu); f[3] = (short)(p23 >> 16);
-        return f;
+        return rc_frag(p01, p23);
     };
     const int z0 = r_begin - 1;
     s16x4 fr[3];                                           // fragments of rows zrow - 1, zrow, zrow + 1 at slots s, s + 1, s + 2 (mod 3)
@@ -430,8 +435,8 @@ template <int CB>
 __global__ __launch_bounds__(256) void rgbconv_fwdblur_kernel(const float* __restrict__ img, const bf16_t* __restrict__ wf, const float* __restrict__ b0,
                                                               bf16_t* __restrict__ y, unsigned char* __restrict__ bits, int B, int H, int W, int ones,
                                                               int nstrips, int nrb, int nit, int dbg) {
-    // nit: 6-row steps per row block (a block stores 6 nit - 2 rows).  dbg (SGX_RGBCONV_DBG, profiling ablations -- wrong results by
-    // design): 4 no output stores, 8 no sign bits
+    // nit: 6-row steps per row block (a block stores 6 nit - 2 rows).  dbg (set only through sgx_rgbconv_tune; profiling ablations --
+    // wrong results by design): 4 no output stores, 8 no sign bits
     constexpr int C = 16 * CB;
     int item = __builtin_amdgcn_readfirstlane((int)(rc_xcd_block() * 4 + (threadIdx.x >> 6)));
     const int sx = item % nstrips; item /= nstrips;
@@ -477,11 +482,7 @@ __global__ __launch_bounds__(256) void rgbconv_dgrad_kernel(const bf16_t* __rest
         }
         return r;
     };
-    auto frag_of = [&](const uint2& u) -> s16x4 {
-        s16x4 f;
-        f[0] = (short)(u.x & 0xffffu); f[1] = (short)(u.x >> 16); f[2] = (short)(u.y & 0xffffu); f[3] = (short)(u.y >> 16);
-        return f;
-    };
+    auto frag_of = [&](const uint2& u) -> s16x4 { return rc_frag(u.x, u.y); };
     Row g0 = load_row(r_begin - 1), g1 = load_row(r_begin);
     Row ring[RC_PF];                                       // rows r + 1 .. r + RC_PF in flight (see the forward kernel)
 #pragma unroll
@@ -547,14 +548,9 @@ __global__ __launch_bounds__(256) void rgbconv_wgrad_kernel(const float* __restr
     uint4 gv[NGV];
     rgb3 iv[NII];
     unsigned okm = 0;
-    auto tile_at = [&](int t, int& b, int& ty0, int& tx0) {
-        const int tx = t % tiles_x; t /= tiles_x;
-        const int ty = t % tiles_y;
-        b = t / tiles_y; ty0 = ty * TH; tx0 = tx * TW;
-    };
     auto load_tile = [&](int t) {
         int b, ty0, tx0;
-        tile_at(t, b, ty0, tx0);
+        rc_tile_at<TH, TW>(t, tiles_x, tiles_y, b, ty0, tx0);
 #pragma unroll
         for (int it = 0; it < NGV; ++it) {
             const int idx = it * 256 + tid, p = idx / VPP, v = idx - p * VPP, r = p / TW, c = p - r * TW;
@@ -731,45 +727,6 @@ static bool rgbconv_shape_ok(int B, int H, int W, int C, int dtype) {
 }
 extern "C" int sgx_rgbconv_ok(int B, int H, int W, int C, int dtype) { return rgbconv_shape_ok(B, H, W, C, dtype) ? 1 : 0; }
 
-extern "C" int sgx_rgbconv_pack(const float* w0, float s0, const float* wr, float sr, const float* br, float bscale, void* wf, void* wd, int C,
-                                void* stream) {
-    SGX_REQUIRE(w0 && wr && wf && wd, SGX_EINVAL, "rgbconv_pack: null argument");
-    SGX_REQUIRE(C == 16 || C == 32, SGX_EUNSUPPORTED, "rgbconv_pack: %d channels (16 or 32)", C);
-    SGX_NOTE(0.0, 0.0, "rgbconv_pack C%d", C);
-    hipLaunchKernelGGL(rgbconv_pack_kernel, dim3(C == 16 ? 12 : 24), dim3(256), 0, (hipStream_t)stream, w0, s0, wr, sr, br, bscale,
-                       static_cast<bf16_t*>(wf), static_cast<bf16_t*>(wd), C);
-    SGX_LAUNCH_CHECK("rgbconv_pack_kernel");
-    return 0;
-}
-
-// persistent grid: as many blocks as fit the chip at once (by LDS; at most 4 per CU), a multiple of 8 (one share per XCD), not
-// more than there are tiles
-static int rc_ncu() { return sgx_ncu(); }
-template <typename K>
-static int rc_per_cu(K kern, int lds_bytes) {              // resident 256-thread blocks per CU (registers AND LDS), at most 4
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, (size_t)lds_bytes) != hipSuccess || n < 1) n = 1;
-    return n > 4 ? 4 : n;
-}
-static int rc_grid(int ntiles, int per_cu) {
-    long g = (long)rc_ncu() * per_cu;
-    if (g > ntiles) g = ntiles;
-    g = (g + 7) / 8 * 8;
-    return (int)g;
-}
-
-template <int CB, int EPI>
-static int launch_rgbconv_fwd(const float* img, const bf16_t* wf, const float* b0, bf16_t* y, unsigned char* bits, int B, int H, int W, int ones,
-                              hipStream_t st, bool one_shot = false) {
-    using G = RcFwd<CB, EPI>;
-    const int tiles_x = W / G::TW, tiles_y = H / G::TH, ntiles = B * tiles_x * tiles_y;
-    sgx_lds_opt_in<rgbconv_fwd_kernel<CB, EPI>>(G::LDS);
-    static const int per_cu = rc_per_cu(rgbconv_fwd_kernel<CB, EPI>, G::LDS);
-    hipLaunchKernelGGL((rgbconv_fwd_kernel<CB, EPI>), dim3((unsigned)(one_shot ? (ntiles + 7) / 8 * 8 : rc_grid(ntiles, per_cu))), dim3(256), G::LDS, st, img, wf, b0, y, bits, B, H, W, ones,
-                       tiles_x, tiles_y, ntiles);
-    SGX_LAUNCH_CHECK("rgbconv_fwd_kernel");
-    return 0;
-}
 // A/B and probe state of the forward kernel.  Read from the environment ONCE per process (SGX_RGBCONV_FWD: 0 row-streaming kernel,
 // 1 LDS-tile kernel with persistent blocks, 2 LDS-tile kernel with one tile per block; SGX_RGBCONV_NIT: 6-row steps per row block,
 // 1..8), changed afterwards only through sgx_rgbconv_tune (tests, tools/rgbconv_probe.py): no getenv on the launch path, and the
@@ -796,6 +753,93 @@ extern "C" int sgx_rgbconv_tune(int fwd_variant, int nit, int dbg) {
     return 0;
 }
 
+// ---- what a call launches: rgbconv_plan decides it, the entry points execute it, sgx_rgbconv_plan reports it without launching
+static int rc_ceil8(long n) { return (int)((n + 7) / 8 * 8); }
+static int rc_nstrips(int W) { return (W + RC_STRIP - 1) / RC_STRIP; }
+static int rc_stream_grid(long items) { return rc_ceil8((items + 3) / 4); }      // four waves (items) per block, a multiple of 8 blocks (rc_xcd_block)
+// persistent grid: as many blocks as fit the chip at once (per_cu resident ones per CU), a multiple of 8 (one share per XCD), not
+// more than there are tiles
+static int rc_grid(int ntiles, int per_cu) {
+    const long fit = (long)sgx_ncu() * per_cu;
+    return rc_ceil8(fit > ntiles ? ntiles : fit);
+}
+template <typename K>
+static int rc_per_cu(K kern, int lds_bytes) {              // resident 256-thread blocks per CU (registers AND LDS), at most 4
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, (size_t)lds_bytes) != hipSuccess || n < 1) n = 1;
+    return n > 4 ? 4 : n;
+}
+enum { RC_WG_PER_CU = 3 };                                 // resident blocks of rgbconv_wgrad_kernel per CU, both channel counts (registers / LDS)
+static_assert(RcWg<2>::TH == RcWg<1>::TH && RcWg<2>::TW == RcWg<1>::TW && RcWg<2>::NOUT == 2 * RcWg<1>::NOUT, "one tile raster, NOUT per 16 channels");
+static int rc_wg_nout(int C) { return C / 16 * RcWg<1>::NOUT; }
+static int rgbconv_wgrad_blocks(int B, int H, int W) {
+    const long ntiles = (long)B * (H / RcWg<1>::TH) * (W / RcWg<1>::TW);
+    return rc_grid((int)(ntiles < (1 << 30) ? ntiles : (1 << 30)), RC_WG_PER_CU);
+}
+static size_t rc_wgrad_ws(int nblk, int C) { return ((size_t)nblk + 1) * rc_wg_nout(C) * sizeof(float); }      // nblk partials and the finished dW'
+extern "C" size_t sgx_rgbconv_wgrad_ws_bytes(int B, int H, int W, int C) {
+    return (B < 1 || H < 8 || W < 64 || (C != 16 && C != 32)) ? 0 : rc_wgrad_ws(rgbconv_wgrad_blocks(B, H, W), C);
+}
+// Everything one call (of a valid shape) will launch: the ints of sgx_rgbconv_plan (include/sgx.h) in its order.  g0, g1, g2 are the kernel's
+// geometry arguments: nstrips, nrb, nit (fwdblur), nstrips, nrb (dgrad), tiles_x, tiles_y, ntiles (the two tile kernels).
+enum { RC_K_PACK = 0, RC_K_FWD = 1, RC_K_FWDBLUR = 2, RC_K_DGRAD = 3, RC_K_WGRAD = 4 };
+struct RcPlan { int kernel, cb, epi, grid, lds, g0, g1, g2, wfinish_grid, chain_grid, per_cu; };
+static RcPlan rgbconv_plan(int entry, int B, int H, int W, int C, int epi, const RcTune& tune) {
+    const int cb = C / 16, nstrips = rc_nstrips(W), nrb32 = (H + RC_ROWS - 1) / RC_ROWS;
+    if (entry == SGX_RGBCONV_PLAN_PACK) return RcPlan{RC_K_PACK, cb, 0, 12 * cb};
+    if (entry == SGX_RGBCONV_PLAN_DGRAD) return RcPlan{RC_K_DGRAD, cb, 0, rc_stream_grid((long)B * nstrips * nrb32), 0, nstrips, nrb32};
+    if (entry == SGX_RGBCONV_PLAN_WGRAD) {
+        const int tiles_x = W / RcWg<1>::TW, tiles_y = H / RcWg<1>::TH;
+        RcPlan p{RC_K_WGRAD, cb, 0, rgbconv_wgrad_blocks(B, H, W), 0, tiles_x, tiles_y, B * tiles_x * tiles_y, (rc_wg_nout(C) + 7) / 8, rgbconv_chain_blocks(C), RC_WG_PER_CU};
+        sgx_by_int<1, 2>(cb, [&](auto c) { p.lds = RcWg<c()>::LDS; });
+        return p;
+    }
+    if (epi && tune.fwd == 0) {                            // the row-streaming kernel (variant 0, the default)
+        // rows per block 6 nit - 2 (two halo rows per block are recomputed): 34 where that still leaves > 3 waves per SIMD slot of the
+        // chip, 22 / 16 for small launches (batch 4 at 1024^2: 14k / 19k waves)          SGX_RGBCONV_NIT overrides (probe)
+        int nit = tune.nit ? tune.nit : 6;                  // 1..8 overrides the row-block heuristic (sgx_rgbconv_tune)
+        if (!tune.nit) {
+            while (nit > 3 && (long)B * nstrips * ((H + 6 * nit - 3) / (6 * nit - 2)) < 3L * 256 * 24) --nit;
+        }
+        const int rb = 6 * nit - 2, nrb = (H + rb - 1) / rb;
+        return RcPlan{RC_K_FWDBLUR, cb, epi, rc_stream_grid((long)B * nstrips * nrb), 0, nstrips, nrb, nit};
+    }
+    RcPlan p{RC_K_FWD, cb, epi};                           // the LDS-tile kernel: epi 0, or variant 1 (persistent blocks) / 2 (one tile per block)
+    sgx_by_int<1, 2>(cb, [&](auto c) {
+        sgx_by_int<0, 1>(epi, [&](auto e) {
+            using G = RcFwd<c(), e()>;
+            p.g0 = W / G::TW; p.g1 = H / G::TH; p.g2 = B * p.g0 * p.g1; p.lds = G::LDS;
+            static const int per_cu = rc_per_cu(rgbconv_fwd_kernel<c(), e()>, G::LDS);       // asked once per instantiation
+            if (epi && tune.fwd == 2) p.grid = rc_ceil8(p.g2);
+            else { p.per_cu = per_cu; p.grid = rc_grid(p.g2, per_cu); }
+        });
+    });
+    return p;
+}
+extern "C" int sgx_rgbconv_plan(int entry, int B, int H, int W, int C, int epi, int* out) {
+    SGX_REQUIRE(out, SGX_EINVAL, "rgbconv_plan: out is NULL");
+    for (int i = 0; i < SGX_RGBCONV_PLAN_INTS; ++i) out[i] = 0;
+    SGX_REQUIRE(entry >= SGX_RGBCONV_PLAN_PACK && entry <= SGX_RGBCONV_PLAN_WGRAD, SGX_EINVAL, "rgbconv_plan: entry %d", entry);
+    SGX_REQUIRE(entry == SGX_RGBCONV_PLAN_PACK ? (C == 16 || C == 32) : rgbconv_shape_ok(B, H, W, C, SGX_BF16), SGX_EUNSUPPORTED,
+                "rgbconv_plan: entry %d, shape B%d %dx%d C%d (sgx_rgbconv_ok == 0; the pack: 16 or 32 channels)", entry, B, H, W, C);
+    SGX_REQUIRE(entry != SGX_RGBCONV_PLAN_FWD || epi == 0 || epi == 1, SGX_EINVAL, "rgbconv_plan: epilogue %d", epi);
+    const RcPlan p = rgbconv_plan(entry, B, H, W, C, epi, rc_tune());
+    const int v[SGX_RGBCONV_PLAN_INTS] = {p.kernel, p.cb, p.epi, p.grid, p.lds, p.g0, p.g1, p.g2, p.wfinish_grid, p.chain_grid, p.per_cu};
+    for (int i = 0; i < SGX_RGBCONV_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int sgx_rgbconv_pack(const float* w0, float s0, const float* wr, float sr, const float* br, float bscale, void* wf, void* wd, int C,
+                                void* stream) {
+    SGX_REQUIRE(w0 && wr && wf && wd, SGX_EINVAL, "rgbconv_pack: null argument");
+    SGX_REQUIRE(C == 16 || C == 32, SGX_EUNSUPPORTED, "rgbconv_pack: %d channels (16 or 32)", C);
+    const RcPlan p = rgbconv_plan(SGX_RGBCONV_PLAN_PACK, 0, 0, 0, C, 0, rc_tune());
+    SGX_NOTE(0.0, 0.0, "rgbconv_pack C%d", C);
+    hipLaunchKernelGGL(rgbconv_pack_kernel, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, w0, s0, wr, sr, br, bscale, as<bf16_t>(wf), as<bf16_t>(wd), C);
+    SGX_LAUNCH_CHECK("rgbconv_pack_kernel");
+    return 0;
+}
+
 extern "C" int sgx_rgbconv_fwd(const float* img, const void* wf, const float* b0, void* y, void* bits, int B, int H, int W, int C, int epi, int ones,
                                int dtype, void* stream) {
     SGX_REQUIRE(img && wf && y, SGX_EINVAL, "rgbconv_fwd: null argument");
@@ -805,32 +849,24 @@ extern "C" int sgx_rgbconv_fwd(const float* img, const void* wf, const float* b0
     const double px = (double)B * H * W;
     SGX_NOTE(2.0 * 27 * C * px, px * (12.0 + 2.0 * C + (epi && bits ? C / 8.0 : 0.0)), "rgbconv%s B%d %dx%d 3->%d", epi ? "+act+blur" : "", B, H, W, C);
     hipStream_t st = (hipStream_t)stream;
-    const bf16_t* w = static_cast<const bf16_t*>(wf);
-    bf16_t* out = static_cast<bf16_t*>(y);
-    unsigned char* bt = static_cast<unsigned char*>(bits);
-    if (epi) {
-        // A/B (read per launch: tools/rgbconv_probe.py): 0 = row-streaming kernel, 1 = LDS-tile kernel with persistent blocks, 2 = LDS-tile
-        // kernel with one tile per block
-        const int variant = rc_tune().fwd;
-        if (variant) return C == 16 ? launch_rgbconv_fwd<1, 1>(img, w, b0, out, bt, B, H, W, ones, st, variant == 2)
-                                    : launch_rgbconv_fwd<2, 1>(img, w, b0, out, bt, B, H, W, ones, st, variant == 2);
-        // rows per block 6 nit - 2 (two halo rows per block are recomputed): 34 where that still leaves > 3 waves per SIMD slot of the
-        // chip, 22 / 16 for small launches (batch 4 at 1024^2: 14k / 19k waves)          SGX_RGBCONV_NIT overrides (probe)
-        const int nstrips = (W + RC_STRIP - 1) / RC_STRIP;
-        const int nit_env = rc_tune().nit;                  // 1..8 overrides the row-block heuristic (sgx_rgbconv_tune)
-        int nit = nit_env ? nit_env : 6;
-        if (!nit_env) {
-            while (nit > 3 && (long)B * nstrips * ((H + 6 * nit - 3) / (6 * nit - 2)) < 3L * 256 * 24) --nit;
+    const RcTune& tune = rc_tune();                         // read per launch (tools/rgbconv_probe.py)
+    const RcPlan p = rgbconv_plan(SGX_RGBCONV_PLAN_FWD, B, H, W, C, epi, tune);
+    sgx_by_int<1, 2>(p.cb, [&](auto cb) {
+        constexpr int CB = cb();
+        if (p.kernel == RC_K_FWDBLUR) {
+            hipLaunchKernelGGL((rgbconv_fwdblur_kernel<CB>), dim3(p.grid), dim3(256), 0, st, img, as<bf16_t>(wf), b0, as<bf16_t>(y), as<unsigned char>(bits), B, H, W, ones,
+                               p.g0, p.g1, p.g2, tune.dbg);
+            return;
         }
-        const int rb = 6 * nit - 2, nrb = (H + rb - 1) / rb;
-        const unsigned grid = (unsigned)((((long)B * nstrips * nrb + 3) / 4 + 7) / 8 * 8);      // (rc_xcd_block)
-        const int dbg = rc_tune().dbg;                      // profiling ablations: only through sgx_rgbconv_tune, never from the environment
-        if (C == 16) hipLaunchKernelGGL((rgbconv_fwdblur_kernel<1>), dim3(grid), dim3(256), 0, st, img, w, b0, out, bt, B, H, W, ones, nstrips, nrb, nit, dbg);
-        else hipLaunchKernelGGL((rgbconv_fwdblur_kernel<2>), dim3(grid), dim3(256), 0, st, img, w, b0, out, bt, B, H, W, ones, nstrips, nrb, nit, dbg);
-        SGX_LAUNCH_CHECK("rgbconv_fwdblur_kernel");
-        return 0;
-    }
-    return C == 16 ? launch_rgbconv_fwd<1, 0>(img, w, b0, out, bt, B, H, W, ones, st) : launch_rgbconv_fwd<2, 0>(img, w, b0, out, bt, B, H, W, ones, st);
+        sgx_by_int<0, 1>(p.epi, [&](auto e) {
+            constexpr int EPI = e();
+            sgx_lds_opt_in<rgbconv_fwd_kernel<CB, EPI>>(p.lds);
+            hipLaunchKernelGGL((rgbconv_fwd_kernel<CB, EPI>), dim3(p.grid), dim3(256), p.lds, st, img, as<bf16_t>(wf), b0, as<bf16_t>(y), as<unsigned char>(bits), B, H, W, ones,
+                               p.g0, p.g1, p.g2);
+        });
+    });
+    SGX_LAUNCH_CHECK(p.kernel == RC_K_FWDBLUR ? "rgbconv_fwdblur_kernel" : "rgbconv_fwd_kernel");
+    return 0;
 }
 
 extern "C" int sgx_rgbconv_dgrad(const void* gz, const void* wd, float* gi, int B, int H, int W, int C, int dtype, void* stream) {
@@ -838,51 +874,38 @@ extern "C" int sgx_rgbconv_dgrad(const void* gz, const void* wd, float* gi, int 
     SGX_REQUIRE(rgbconv_shape_ok(B, H, W, C, dtype), SGX_EUNSUPPORTED, "rgbconv_dgrad: shape B%d %dx%d C%d dtype %d (sgx_rgbconv_ok == 0)", B, H, W, C, dtype);
     const double px = (double)B * H * W;
     SGX_NOTE(2.0 * 27 * C * px, px * (12.0 + 2.0 * C), "rgbconv_dgrad B%d %dx%d %d->3", B, H, W, C);
-    hipStream_t st = (hipStream_t)stream;
-    const int nstrips = (W + RC_STRIP - 1) / RC_STRIP, nrb = (H + RC_ROWS - 1) / RC_ROWS;
-    const unsigned grid = (unsigned)((((long)B * nstrips * nrb + 3) / 4 + 7) / 8 * 8);          // (rc_xcd_block)
-    if (C == 16) hipLaunchKernelGGL((rgbconv_dgrad_kernel<1>), dim3(grid), dim3(256), 0, st, static_cast<const bf16_t*>(gz), static_cast<const bf16_t*>(wd), gi, B, H, W, nstrips, nrb);
-    else hipLaunchKernelGGL((rgbconv_dgrad_kernel<2>), dim3(grid), dim3(256), 0, st, static_cast<const bf16_t*>(gz), static_cast<const bf16_t*>(wd), gi, B, H, W, nstrips, nrb);
+    const RcPlan p = rgbconv_plan(SGX_RGBCONV_PLAN_DGRAD, B, H, W, C, 0, rc_tune());
+    sgx_by_int<1, 2>(p.cb, [&](auto cb) {
+        constexpr int CB = cb();
+        hipLaunchKernelGGL((rgbconv_dgrad_kernel<CB>), dim3(p.grid), dim3(256), 0, (hipStream_t)stream, as<bf16_t>(gz), as<bf16_t>(wd), gi, B, H, W, p.g0, p.g1);
+    });
     SGX_LAUNCH_CHECK("rgbconv_dgrad_kernel");
     return 0;
 }
 
-static int rgbconv_wgrad_blocks(int B, int H, int W) {
-    const long ntiles = (long)B * (H / 8) * (W / 64);
-    return rc_grid((int)(ntiles < (1 << 30) ? ntiles : (1 << 30)), 3);     // 3 resident blocks per CU for both channel counts (registers / LDS)
-}
-extern "C" size_t sgx_rgbconv_wgrad_ws_bytes(int B, int H, int W, int C) {
-    if (B < 1 || H < 8 || W < 64 || (C != 16 && C != 32)) return 0;
-    return ((size_t)rgbconv_wgrad_blocks(B, H, W) + 1) * C * 48 * sizeof(float);
-}
 extern "C" int sgx_rgbconv_wgrad(const float* img, const void* gz, int ones, const float* w0, float s0, const float* wr, float sr, const float* br,
                                  float bscale, float* dw0, float* db0, float* dwr, float* dbr, int acc, void* ws, size_t ws_bytes, int B, int H, int W,
                                  int C, int dtype, void* stream) {
     SGX_REQUIRE(img && gz && w0 && wr && ws, SGX_EINVAL, "rgbconv_wgrad: null argument");
     SGX_REQUIRE(rgbconv_shape_ok(B, H, W, C, dtype), SGX_EUNSUPPORTED, "rgbconv_wgrad: shape B%d %dx%d C%d dtype %d (sgx_rgbconv_ok == 0)", B, H, W, C, dtype);
-    SGX_REQUIRE(ws_bytes >= sgx_rgbconv_wgrad_ws_bytes(B, H, W, C), SGX_EWORKSPACE, "rgbconv_wgrad: workspace %zu < %zu", ws_bytes,
-                sgx_rgbconv_wgrad_ws_bytes(B, H, W, C));
+    const RcPlan p = rgbconv_plan(SGX_RGBCONV_PLAN_WGRAD, B, H, W, C, 0, rc_tune());
+    SGX_REQUIRE(ws_bytes >= rc_wgrad_ws(p.grid, C), SGX_EWORKSPACE, "rgbconv_wgrad: workspace %zu < %zu", ws_bytes, rc_wgrad_ws(p.grid, C));
     SGX_REQUIRE(ones || (!db0 && !dbr), SGX_EINVAL, "rgbconv_wgrad: bias gradients need the bias channel (ones = 1)");
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = rgbconv_wgrad_blocks(B, H, W), nout = C * 48;
-    const int tiles_x = W / 64, tiles_y = H / 8, ntiles = B * tiles_x * tiles_y;
-    float* part = static_cast<float*>(ws);
-    float* dwp = part + (size_t)nblk * nout;
+    const int nblk = p.grid, nout = rc_wg_nout(C);
+    float *part = as<float>(ws), *dwp = part + (size_t)nblk * nout;
     const double px = (double)B * H * W;
     SGX_NOTE(2.0 * 36 * C * px, px * (12.0 + 2.0 * C), "rgbconv_wgrad B%d %dx%d 3x%d", B, H, W, C);
-    if (C == 16) {
-        sgx_lds_opt_in<rgbconv_wgrad_kernel<1>>(RcWg<1>::LDS);
-        hipLaunchKernelGGL((rgbconv_wgrad_kernel<1>), dim3((unsigned)nblk), dim3(256), RcWg<1>::LDS, st, img, static_cast<const bf16_t*>(gz), part, B, H, W,
-                           ones, tiles_x, tiles_y, ntiles);
-    } else {
-        sgx_lds_opt_in<rgbconv_wgrad_kernel<2>>(RcWg<2>::LDS);
-        hipLaunchKernelGGL((rgbconv_wgrad_kernel<2>), dim3((unsigned)nblk), dim3(256), RcWg<2>::LDS, st, img, static_cast<const bf16_t*>(gz), part, B, H, W,
-                           ones, tiles_x, tiles_y, ntiles);
-    }
+    sgx_by_int<1, 2>(p.cb, [&](auto cb) {
+        constexpr int CB = cb();
+        sgx_lds_opt_in<rgbconv_wgrad_kernel<CB>>(p.lds);
+        hipLaunchKernelGGL((rgbconv_wgrad_kernel<CB>), dim3(nblk), dim3(256), p.lds, st, img, as<bf16_t>(gz), part, B, H, W, ones, p.g0, p.g1, p.g2);
+    });
     SGX_LAUNCH_CHECK("rgbconv_wgrad_kernel");
-    hipLaunchKernelGGL(rgbconv_wfinish_kernel, dim3((unsigned)((nout + 7) / 8)), dim3(256), 0, st, (const float*)part, dwp, nblk, nout);
+    hipLaunchKernelGGL(rgbconv_wfinish_kernel, dim3(p.wfinish_grid), dim3(256), 0, st, (const float*)part, dwp, nblk, nout);
     SGX_LAUNCH_CHECK("rgbconv_wfinish_kernel");
-    hipLaunchKernelGGL(rgbconv_chain_kernel, dim3((unsigned)rgbconv_chain_blocks(C)), dim3(256), 0, st, (const float*)dwp, w0, s0, wr, sr, br, bscale, dw0, db0, dwr, dbr, acc, C);
+    hipLaunchKernelGGL(rgbconv_chain_kernel, dim3(p.chain_grid), dim3(256), 0, st, (const float*)dwp, w0, s0, wr, sr, br, bscale, dw0, db0, dwr, dbr, acc, C);
     SGX_LAUNCH_CHECK("rgbconv_chain_kernel");
     return 0;
 }
+

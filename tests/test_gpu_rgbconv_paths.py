@@ -4,7 +4,8 @@ integers at unit scales; this file holds them per element.
 
 Each row is one call through native.lib() under the library's profiler (epilogue_runner.profiled): the return code is 0, the kernels that
 ran and their grids, blocks and dynamic LDS sizes are what rgbconv_ref.plan restates from the row's arguments (the persistent grid of
-rgbconv_fwd_kernel, sized by an occupancy query, by its properties), every output -- the two packs, y, the sign bits, gi, the four parameter
+rgbconv_fwd_kernel, sized by an occupancy query, by its properties) and, every one by value, what sgx_rgbconv_plan reported for the call
+(tests/test_rgbconv_plan.py holds the query to the restated rules without a device), every output -- the two packs, y, the sign bits, gi, the four parameter
 gradients and the whole wgrad workspace -- is a streaming_ref.Guarded view pre-filled with NaN bytes whose bands come back untouched, and
 the values meet rgbconv_ref's criteria: bit for bit on the integer rows, the per-element bounds against the fp64 restatement otherwise.
 sgx_rgbconv_tune's state is process-wide: every test leaves (-1, 0, 0) behind (the autouse fixture), whatever it raised."""
@@ -18,6 +19,7 @@ import epilogue_ref as ER
 import epilogue_runner as ERUN
 import rgbconv_ref as RR
 import streaming_ref as SR
+import test_rgbconv_plan as TRP
 from epilogue_runner import DEV, native, p
 
 pytestmark = pytest.mark.gpu
@@ -62,8 +64,12 @@ def G(shape, dtype=F32):
     return SR.Guarded(shape, dtype, DEV)
 
 
-def launch(c, call):
-    """The call under the profiler: rc 0 (profiled checks it), the row's kernels in order, the restated geometry -> the grids."""
+def launch(c, call, B=None):
+    """The call under the profiler: rc 0 (profiled checks it), the row's kernels in order, the restated geometry, and kernels and geometry
+    as the library's own query reports them under the tune state of the call (B: the batch size where the row leaves it to the device)
+    -> the grids."""
+    a = c.args
+    q = TRP.lib_plan(native().lib(), TRP.ENTRY[c.entry], B or a.get("B") or 0, a.get("H") or 0, a.get("W") or 0, a["C"], a.get("epi", 0))
     ran = ERUN.profiled(c.id, c.entry, call)
     kernels, launches = RR.plan(c, ncu())
     assert tuple(ran) == tuple(c.kernels) == tuple(kernels), f"{c.id}: launched {ran}, the row says {c.kernels}, the rules {kernels} ({c.why})"
@@ -71,6 +77,7 @@ def launch(c, call):
     assert len(got) == len(launches), (c.id, got)
     for (g, b, lds), (wg, wb, wl) in zip(got, launches):
         assert (b, lds) == (wb, wl) and g[1:] == (1, 1) and (wg is None or g == wg), f"{c.id}: launch geometry {got}, restated {launches}"
+    assert (tuple(ran), got) == TRP.launches_of(q), f"{c.id}: launched {ran} as {got}, sgx_rgbconv_plan reported {q}"
     return [g[0] for g, _, _ in got]
 
 
@@ -200,7 +207,7 @@ def run_fwd_persistent(L, N, c):
     N.check(L.sgx_rgbconv_tune(a["variant"], 0, 0), "sgx_rgbconv_tune")
     b0 = dev(o["b0"]) if epi else None
     probe, y0 = dev(RR.image(B0, H, W, "int")), G((B0, H, W, C), BF16)
-    full = launch(c, fwd_call(L, N, probe, wf, b0, y0, None, a, B0))[0]
+    full = launch(c, fwd_call(L, N, probe, wf, b0, y0, None, a, B0), B0)[0]
     RR.check_rc_grid(full, B0 * per_image, ncu())
     del y0, probe
     B = RR.persistent_batch(full, per_image)
@@ -209,7 +216,7 @@ def run_fwd_persistent(L, N, c):
     img64 = RR.image(B, H, W, "int")
     img = dev(img64)
     y, bits = G((B, H, W, C), BF16), G((B, H, W, C // 8), U8) if epi else None
-    grid = launch(c, fwd_call(L, N, img, wf, b0, y, bits, a, B))[0]
+    grid = launch(c, fwd_call(L, N, img, wf, b0, y, bits, a, B), B)[0]
     counts = RR.sched_counts(grid, ntiles)
     assert grid == full < ntiles and 1 in counts and 2 in counts, (grid, full, ntiles, sorted(set(counts)))
     y.assert_intact(f"{c.id} y")

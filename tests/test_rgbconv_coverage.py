@@ -1,4 +1,4 @@
-"""CPU side of tests/test_gpu_rgbconv_paths.py: (a) each of the ten hipLaunchKernelGGL sites of csrc/rgbconv.hip is claimed by a row of
+"""CPU side of tests/test_gpu_rgbconv_paths.py: (a) each of the seven hipLaunchKernelGGL sites of csrc/rgbconv.hip (one per kernel) is claimed by a row of
 rgbconv_ref.CASES, every instantiation the launchers can reach is named by a row, every __global__ of the file is in the table; (b) the rows
 reach what they are there for, computed from the restated launcher rules; (c) the references alone have the properties the GPU rows rely on,
 and agree with autograd through the two layers; the contract rejections return before any launch; (d) the criteria pass a numpy fp32
@@ -35,14 +35,15 @@ def source():
 
 
 # ---------------------------------------------------------------------------------------------------------------- (a) the scan
-GENERIC = ("rgbconv_fwd_kernel", "<CB, EPI>")                # the one site that is generic in both template arguments: launch_rgbconv_fwd<CB, EPI>
+GENERIC = ("rgbconv_fwd_kernel", "<CB, EPI>")                # the one site that is generic in two template arguments: sgx_by_int<1, 2> around sgx_by_int<0, 1>
 
 
 def unclaimed(sites, cases):
-    """test_streaming_coverage.unclaimed, and for the generic site every instantiation sgx_rgbconv_fwd can ask launch_rgbconv_fwd for."""
+    """test_streaming_coverage.unclaimed (every value of the sgx_by_int list around a site), and for the generic site every pair of the two
+    lists: the scan reads the innermost list only."""
     miss = TSC.unclaimed(sites, cases, {})
     named = {k for c in cases for k in c.kernels}
-    if GENERIC in sites and GENERIC[0] + GENERIC[1] not in miss:
+    if any(s[:2] == GENERIC for s in sites) and GENERIC[0] + GENERIC[1] not in miss:
         lack = [f"<{cb}, {epi}>" for cb in (1, 2) for epi in (0, 1) if RR.fwd_kernel(cb, epi) not in named]
         if lack:
             miss.append(f"{GENERIC[0]}{GENERIC[1]} for {lack}")
@@ -51,10 +52,13 @@ def unclaimed(sites, cases):
 
 def test_every_launch_site_of_rgbconv_hip_has_a_row():
     sites = TSC.launch_sites(RGB)
-    # pack 1, the LDS-tile forward 1 (generic), the row-streaming forward 2, dgrad 2, wgrad 2, wfinish 1, chain 1
-    assert len(sites) == 10 and collections.Counter(s[0] for s in sites) == {"rgbconv_pack_kernel": 1, "rgbconv_fwd_kernel": 1, "rgbconv_fwdblur_kernel": 2, "rgbconv_dgrad_kernel": 2,
-                                                                              "rgbconv_wgrad_kernel": 2, "rgbconv_wfinish_kernel": 1, "rgbconv_chain_kernel": 1}, sites
-    assert GENERIC in sites and all(s[1] in ("<1>", "<2>") for s in sites if s[0] in ("rgbconv_fwdblur_kernel", "rgbconv_dgrad_kernel", "rgbconv_wgrad_kernel"))
+    # one site per kernel; the three <CB> kernels inside sgx_by_int<1, 2>, the LDS-tile forward inside that and sgx_by_int<0, 1>
+    assert len(sites) == 7 and collections.Counter(s[0] for s in sites) == {k: 1 for k in RR.KERNELS}, sites
+    by = {s[0]: s[1:] for s in sites}
+    for k in ("rgbconv_fwdblur_kernel", "rgbconv_dgrad_kernel", "rgbconv_wgrad_kernel"):
+        assert by[k] == ("<CB>", {"cb()": ["1", "2"], "CB": ["1", "2"]}), (k, by[k])
+    assert by[GENERIC[0]] == (GENERIC[1], {"e()": ["0", "1"], "EPI": ["0", "1"]}), by[GENERIC[0]]
+    assert all(by[k] == ("",) for k in (RR.PACK, RR.WFINISH, RR.CHAIN))
     assert unclaimed(sites, RR.CASES) == []
     kernels = set(re.findall(r"__global__\s+(?:__launch_bounds__\(\d+\)\s+)?void\s+([A-Za-z_0-9]+)", source()))
     assert kernels == set(RR.KERNELS), kernels ^ set(RR.KERNELS)
@@ -74,11 +78,13 @@ def test_a_new_site_or_a_dropped_row_is_noticed():
     assert unclaimed(sites + [("rgbconv_fwdblur_kernel", "<4>")], RR.CASES) == ["rgbconv_fwdblur_kernel<4>"]
     assert unclaimed(sites + [("rgbconv_wgrad2_kernel", "")], RR.CASES) == ["rgbconv_wgrad2_kernel"]
     without = lambda k: [c for c in RR.CASES if k not in c.kernels]
-    for k in ("rgbconv_fwdblur_kernel<2>", "rgbconv_dgrad_kernel<1>", "rgbconv_wgrad_kernel<2>"):
-        assert unclaimed(sites, without(k)) == [k]
-    assert unclaimed(sites, without(RR.fwd_kernel(2, 0))) == ["rgbconv_fwd_kernel<CB, EPI> for ['<2, 0>']"]
-    assert unclaimed(sites, without(RR.fwd_kernel(1, 1))) == ["rgbconv_fwd_kernel<CB, EPI> for ['<1, 1>']"]
-    assert unclaimed(sites, [c for c in RR.CASES if c.entry != "sgx_rgbconv_wgrad"]) == ["rgbconv_wgrad_kernel<1>", "rgbconv_wgrad_kernel<2>", "rgbconv_wfinish_kernel",
+    for k in ("rgbconv_fwdblur_kernel", "rgbconv_dgrad_kernel", "rgbconv_wgrad_kernel"):
+        for cb in (1, 2):
+            assert unclaimed(sites, without(f"{k}<{cb}>")) == [f"{k}<CB> for [{cb}]"]
+    for cb in (1, 2):
+        for epi in (0, 1):
+            assert unclaimed(sites, without(RR.fwd_kernel(cb, epi))) == [f"rgbconv_fwd_kernel<CB, EPI> for ['<{cb}, {epi}>']"]
+    assert unclaimed(sites, [c for c in RR.CASES if c.entry != "sgx_rgbconv_wgrad"]) == ["rgbconv_wgrad_kernel<CB>", "rgbconv_wfinish_kernel",
                                                                                          "rgbconv_chain_kernel"]
 
 
