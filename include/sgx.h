@@ -354,6 +354,42 @@ int sgx_ada_gates_n(const float* gu, int gu_stride, int n_ops, const float* stat
 int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
                         void* stream);
 int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream);
+/* The colour transformations, the third augmentation group of the ADA paper: policy_bits a subset of 256 = brightness, 512 = contrast,
+ * 1024 = lumaflip, 2048 = hue, 4096 = saturation, applied in that order AFTER the ops above, composed per image into one affine map of
+ * the RGB vector of fp32 [B][H][W][3] images.  u: DEVICE fp32, row b at u + b * u_stride (u_stride >= 8), eight uniforms in [0,1); with
+ * z(ua, ub) = clamp(sqrt(-2 ln(1 - ua)) cos(2 pi ub), -3, 3):
+ *   b = 0.2 z(u0, u1) when brightness is on for the image, else 0
+ *   c = 2^(0.5 z(u2, u3)) when contrast is on, else 1
+ *   sigma = 1 - 2 min(floor(2 u4), 1) when lumaflip is on (-1 for u4 >= 0.5), else 1
+ *   theta = 2 pi (u5 - 0.5) when hue is on, else 0
+ *   s = 2^(z(u6, u7)) when saturation is on, else 1
+ * With v = (1,1,1)/sqrt(3), P = v v^T and K = (1/sqrt(3)) [0 -1 1; 1 0 -1; -1 1 0] (the cross-product matrix of v) the map is the paper's
+ * composition Sat Hue Luma Contrast Brightness of each pixel's RGB vector x:
+ *   y = M x + t,   M = c [sigma P + s (cos(theta) (I - P) + sin(theta) K)],   t = c sigma b (1,1,1).
+ * M is circulant, rows (D L U), (U D L), (L U D):  D = a + 2 (d/3),  L = (a - d/3) - e,  U = (a - d/3) + e  with  a = (c sigma)/3,
+ * d = (c s) cos(theta),  e = ((c s) sin(theta)) * 0.57735027  (fp32, every product, quotient, sum and difference rounded on its own as
+ * bracketed; the precise logf / cosf / sinf / exp2f / sqrtf; cos = 1 and sin = 0 exactly when hue is off; t = (c sigma) * b).  Pixels
+ * that the earlier stages zeroed (the padding of the translation and of the resample, the cutout) are transformed like any other and
+ * come out as t.  An op is on for an image when its bit is in policy_bits and either gu == NULL or its gate uniform is strictly below
+ * p = state[0] read on the device: gu row b at gu + b * gu_stride (gu_stride >= 5), columns 0..4 gating brightness, contrast, lumaflip,
+ * hue, saturation; gu and state are both given or both NULL.
+ * sgx_ada_color_matrix: one launch writes mat[b][0..8] = M (row major) and mat[b][9..11] = t of every image, fp32 [B][12].  Exact rows:
+ *   an image with all five ops off gets exactly (1,0,0, 0,1,0, 0,0,1, 0,0,0): that row is the identity flag -- the pass copies such an
+ *   image bit for bit; an image without a flip (lumaflip off, or on with sigma = 1), with hue and saturation off gets exactly c on the
+ *   diagonal and +0 off it (a branch, not 1/3 + 2/3); with theta = 0 (hue off) e is +0, so L == U bit for bit: a flip alone gives a
+ *   symmetric row.  Made once per D evaluation; the forward, the linear part, the adjoint and the R1 double backward read the table,
+ *   never p.
+ * sgx_ada_color: x != y, any H, W >= 1, one pass over the batch;
+ *   adjoint = 0:  y_k = ((M_k0 x_0 + M_k1 x_1) + M_k2 x_2) (+ t_k when with_bias)
+ *   adjoint = 1:  y_k = ((M_0k x_0 + M_1k x_1) + M_2k x_2); with_bias must be 0
+ *   every product and sum rounded to fp32 on its own in that order, so a float32 restatement reproduces the output bit for bit and the
+ *   adjoint's coefficients are the forward's.  An image whose row compares equal to the identity row is copied instead, bit for bit
+ *   (-0, infinities and NaN payloads included, which 1 x + 0 x' would not preserve).  No workspace, no atomics, nothing written
+ *   outside y.  With H W % 4 == 0 and 16-byte aligned bases a lane owns four consecutive pixels (three 16-byte loads and stores),
+ *   else one. */
+int sgx_ada_color_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
+                         void* stream);
+int sgx_ada_color(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, int with_bias, void* stream);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

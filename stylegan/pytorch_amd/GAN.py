@@ -356,7 +356,8 @@ class Discriminator(nn.Module):
                  ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
-        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso' ('' = off); parsed here so that a bad policy fails at construction
+        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation' ('' = off); parsed here
+        # so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
         if self._diffaug_bits and num_channels != 3:
@@ -440,13 +441,38 @@ class Discriminator(nn.Module):
     geom_override = None
     geom_gate_override = None
 
+    # and for the colour ops (brightness, contrast, lumaflip, hue, saturation): their [B,8] draws and, under ADA, their [B,5] gate uniforms
+    color_override = None
+    color_gate_override = None
+
     def _diffaug(self, img):
-        """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage."""
+        """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage,
+        then the colour stage."""
         if self._diffaug_bits & F.DIFFAUG_PIXEL_MASK:
             img = self._diffaug_pixel(img, self._diffaug_bits & F.DIFFAUG_PIXEL_MASK)
         if self._diffaug_bits & F.DIFFAUG_GEOM_MASK:
             img = self._diffaug_geom(img)
+        if self._diffaug_bits & F.DIFFAUG_COLOR_MASK:
+            img = self._diffaug_color(img)
         return img
+
+    def _diffaug_color(self, img):
+        """brightness, contrast, lumaflip, hue, saturation: one draw of its own per D evaluation ([B,8]; [B,13] under ADA, columns 8..12
+        the gates), turned into the per-image table {M, t} ONCE, here; the pass, its adjoint, its linear part and the R1 double backward
+        of this evaluation read the table, never p."""
+        B = img.shape[0]
+        u, gu = self.color_override, self.color_gate_override
+        self._override_ok(u, B, 8, "color_override")
+        if not self.ada:
+            if u is None:
+                u = torch.rand(B, 8, device=img.device)
+            return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits))
+        self._override_ok(gu, B, 5, "color_gate_override")
+        if u is None or gu is None:
+            r = torch.rand(B, 13, device=img.device)
+            u = r[:, :8] if u is None else u
+            gu = r[:, 8:] if gu is None else gu
+        return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits, gu, self.ada_state))
 
     def _diffaug_geom(self, img):
         """scale, rotate, aniso: one draw of its own per D evaluation ([B,5]; [B,8] under ADA, columns 5..7 the gates), turned into the
@@ -1006,7 +1032,9 @@ class StyleGAN:
                (self.dis.ada_target, self.dis.ada_interval, self.dis.ada_kimg) if self._ada_on() else None,   # ... baked into the update launch
                None if not self._ada_on() or self.dis.ada_gate_override is None else self.dis.ada_gate_override.data_ptr(),
                None if self.dis.geom_override is None else self.dis.geom_override.data_ptr(),
-               None if not self._ada_on() or self.dis.geom_gate_override is None else self.dis.geom_gate_override.data_ptr())
+               None if not self._ada_on() or self.dis.geom_gate_override is None else self.dis.geom_gate_override.data_ptr(),
+               None if self.dis.color_override is None else self.dis.color_override.data_ptr(),
+               None if not self._ada_on() or self.dis.color_gate_override is None else self.dis.color_gate_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)

@@ -130,7 +130,7 @@ def default_cfg():
             "gen": {"latent_size": 512, "mapping_layers": 4, "blur_filter": [1, 2, 1], "truncation_psi": 0.7,
                     "truncation_cutoff": 8},                                                      # :61-67
             "dis": {"use_wscale": True, "blur_filter": [1, 2, 1],                                 # :72-74
-                    "diffaug_policy": "",             # DiffAugment of D's input, e.g. "color,translation,cutout" ('' = off; xflip, rot90: ADA's pixel blitting; scale, rotate, aniso: its geometric group, last)
+                    "diffaug_policy": "",             # DiffAugment of D's input, e.g. "color,translation,cutout" ('' = off; xflip, rot90: ADA's pixel blitting; scale, rotate, aniso: its geometric group; brightness, contrast, lumaflip, hue, saturation: its colour group, last)
                     # ADA (Karras et al., NeurIPS 2020): each op of the policy with probability p, p steered so that
                     # E[sign(D(real))] meets ada_target (0 = off, the paper uses 0.6); one controller update per ada_interval
                     # D steps; ada_kimg thousand images for p to travel from 0 to 1; p starts at ada_p_init

@@ -2438,16 +2438,22 @@ DIFFAUG_GEOM_OPS = ("scale", "rotate", "aniso")
 DIFFAUG_GEOM_BITS = {"scale": 32, "rotate": 64, "aniso": 128}
 DIFFAUG_GEOM_MASK = 32 | 64 | 128
 DIFFAUG_PIXEL_MASK = 31                                                      # the bits the DiffAugment / blitting entry points take
+# the colour group of the ADA paper, applied last by its own kernels (``sgx_ada_color``, further down)
+DIFFAUG_COLOR_OPS = ("brightness", "contrast", "lumaflip", "hue", "saturation")
+DIFFAUG_COLOR_BITS = {"brightness": 256, "contrast": 512, "lumaflip": 1024, "hue": 2048, "saturation": 4096}
+DIFFAUG_COLOR_MASK = 256 | 512 | 1024 | 2048 | 4096
 
 
 def diffaug_policy_bits(policy):
-    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout,scale,rotate,aniso``
-    in that (canonical) order, each at most once; '' or None: no augmentation.  Anything else raises ValueError."""
+    """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout,scale,rotate,aniso,
+    brightness,contrast,lumaflip,hue,saturation`` in that (canonical) order, each at most once; '' or None: no augmentation.  Anything
+    else raises ValueError."""
     if policy is None:
         return 0
     if not isinstance(policy, str):
         raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
-    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS
+    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS
+    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS}
     bits, last = 0, -1
     for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
         if name not in order:
@@ -2455,7 +2461,7 @@ def diffaug_policy_bits(policy):
         k = order.index(name)
         if k <= last:
             raise ValueError(f"DiffAugment policy {policy!r}: ops must appear once each, in the order {','.join(order)}")
-        bits |= DIFFAUG_BITS[name] if name in DIFFAUG_BITS else DIFFAUG_GEOM_BITS[name]
+        bits |= known[name]
         last = k
     return bits
 
@@ -2662,3 +2668,91 @@ class AdaGeomAdjFn(Function):
     def backward(ctx, gg):
         mat, = ctx.saved_tensors
         return _bcall(AdaGeomFn, gg, mat), None
+
+
+# The colour group of the ADA paper (brightness, contrast, lumaflip, hue, saturation; ``sgx_ada_color_matrix`` / ``sgx_ada_color``,
+# include/sgx.h): one table of per-image affine maps {M, t} of the RGB vector per D evaluation and one streaming pass.  The chain
+# AdaColorFn (M x + t) -> AdaColorAdjFn (M^T g) -> AdaColorLinFn (M x) -> AdaColorAdjFn closes under differentiation, so the R1 double
+# backward runs through it.  All three save only the table.
+def ada_color_matrix(u, bits, gu=None, state=None):
+    """u fp32 [B,8] draws (rows of a wider draw are read in place) -> the fp32 [B,12] table {M row major, t} of the colour ops in ``bits``
+    (256 brightness, 512 contrast, 1024 lumaflip, 2048 hue, 4096 saturation); with ``gu`` fp32 [B,5] gate uniforms and the ADA ``state``,
+    an op is on for image b iff gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0, 0,1,0, 0,0,1, 0,0,0)."""
+    if u.dim() != 2 or u.shape[1] != 8 or u.dtype != torch.float32:
+        raise N.SgxError(f"ada_color_matrix: need fp32 [B,8] draws, got {tuple(u.shape)} {u.dtype}")
+    if u.stride(1) != 1 or u.stride(0) < 8:
+        u = _c(u)
+    if (gu is None) != (state is None):
+        raise N.SgxError("ada_color_matrix: gate uniforms and the ADA state come together or not at all")
+    B = u.shape[0]
+    gp, gs = None, 0
+    if gu is not None:
+        if tuple(gu.shape) != (B, 5) or gu.dtype != torch.float32 or gu.device != u.device:
+            raise N.SgxError(f"ada_color_matrix: need fp32 [{B},5] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
+        if gu.stride(1) != 1 or gu.stride(0) < 5:
+            gu = _c(gu)
+        _ada_state_ok(state, u.device, "ada_color_matrix")
+        gp, gs = gu.data_ptr(), gu.stride(0)
+    if not u.is_cuda:
+        raise N.SgxError("libsgx_hip kernels need GPU tensors (no CPU fallback exists for this path)")
+    mat = torch.empty(B, 12, dtype=torch.float32, device=u.device)
+    N.check(N.lib().sgx_ada_color_matrix(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_COLOR_MASK, N.ptr(mat), B,
+                                         N.stream()), "sgx_ada_color_matrix")
+    return mat
+
+
+def _ada_color(x, mat, adjoint, with_bias):
+    x = _c(x)
+    if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
+        raise N.SgxError(f"ada_color: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    B, H, W, _ = x.shape
+    if tuple(mat.shape) != (B, 12) or mat.dtype != torch.float32 or mat.device != x.device:
+        raise N.SgxError(f"ada_color: need an fp32 [{B},12] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
+    y = torch.empty_like(x)
+    N.check(N.lib().sgx_ada_color(N.ptr(x), N.ptr(y), N.ptr(_c(mat)), B, H, W, int(adjoint), int(with_bias), N.stream()), "sgx_ada_color")
+    return y
+
+
+class AdaColorFn(Function):
+    """y = M x + t per pixel under the table ``mat`` (no gradient); backward = the adjoint (AdaColorAdjFn), none when x needs no
+    gradient (the D step's fakes)."""
+
+    @staticmethod
+    def forward(ctx, x, mat):
+        ctx.save_for_backward(mat)
+        return _ada_color(x, mat, False, True)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        mat, = ctx.saved_tensors
+        return _bcall(AdaColorAdjFn, g, mat), None
+
+
+class AdaColorAdjFn(Function):
+    """z = M^T g; backward = M without the bias (AdaColorLinFn)."""
+
+    @staticmethod
+    def forward(ctx, g, mat):
+        ctx.save_for_backward(mat)
+        return _ada_color(g, mat, True, False)
+
+    @staticmethod
+    def backward(ctx, gg):
+        mat, = ctx.saved_tensors
+        return _bcall(AdaColorLinFn, gg, mat), None
+
+
+class AdaColorLinFn(Function):
+    """M x (the linear part of AdaColorFn); backward = AdaColorAdjFn."""
+
+    @staticmethod
+    def forward(ctx, x, mat):
+        ctx.save_for_backward(mat)
+        return _ada_color(x, mat, False, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        mat, = ctx.saved_tensors
+        return _bcall(AdaColorAdjFn, g, mat), None
