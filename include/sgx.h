@@ -390,6 +390,24 @@ int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W
 int sgx_ada_color_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
                          void* stream);
 int sgx_ada_color(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, int with_bias, void* stream);
+/* Host-only query: what the image pass `entry` (SGX_AUG_PLAN_DIFFAUG / _GATED / _BLIT / _GEOM / _COLOR for sgx_diffaug / sgx_diffaug_gated /
+ * sgx_diffaug_blit / sgx_ada_geom / sgx_ada_color) will launch for B images of H x W.  The entry points execute the same plan.  aligned:
+ * both image bases are 16-byte aligned.  policy_bits is read for the first three entries only, with_bias for the colour pass only.
+ * out[SGX_AUG_PLAN_INTS]: [0] the number of launches (1 or 2), then ten ints per launch, in launch order:
+ *   +0  the kernel: 0 diffaug_sum_kernel<P, MODE, GATED>, 1 diffaug_apply_kernel<P, ADJ, GATED>, 2 diffaug_blit_sum_kernel<P, MODE>,
+ *       3 diffaug_blit_row_kernel<P, ADJ>, 4 diffaug_blit_tile_kernel<ADJ>, 5 ada_geom_px_kernel<ADJ>, 6 ada_geom_tile_kernel<ADJ>,
+ *       7 ada_color_px_kernel<ADJ, BIAS>, 8 ada_color_vec_kernel<ADJ, BIAS>
+ *   +1  P, pixels per lane (1 or 4);  +2  MODE of the two sum kernels (0 the input itself, 2 the adjoint's gather), ADJ (0 / 1) of the
+ *       others;  +3  GATED;  +4  BIAS -- each 0 for a kernel without that template argument
+ *   +5  grid x, +6 grid y (= B); every block is 256 threads, no launch has dynamic LDS
+ *   +7  nparts: partial sums per image (the workspace is 4 B nparts bytes: sgx_diffaug_ws_bytes);  +8  tiles of 32 x 32 pixels per row of
+ *       tiles (the two tile kernels);  +9  H W (the colour kernels) -- the geometry arguments the kernel receives, 0 where it takes none
+ * A policy with colour launches the sum pass, then the apply pass.  Returns 0, or what the entry itself returns for these arguments
+ * (SGX_EINVAL: B outside 1..65535, H or W < 1, policy bits outside the entry's ops, rot90 with H != W, the colour adjoint with a bias;
+ * SGX_EUNSUPPORTED: 3 H W >= 2^31), or SGX_EINVAL for an unknown entry or a NULL out.  out is zeroed on every error but the last. */
+enum { SGX_AUG_PLAN_DIFFAUG = 0, SGX_AUG_PLAN_GATED = 1, SGX_AUG_PLAN_BLIT = 2, SGX_AUG_PLAN_GEOM = 3, SGX_AUG_PLAN_COLOR = 4 };
+#define SGX_AUG_PLAN_INTS 21
+int sgx_aug_plan(int entry, int B, int H, int W, int policy_bits, int adjoint, int with_bias, int aligned, int* out);
 /* the generator's output in one pass: img = alpha * to_rgb(x) + beta * nearest_up2(low) (models/GAN.py:199-202 with the 1x1
  * convolution commuted in front of the upsample): low = [B][H/2][W/2][3] fp32.  ab_dev != NULL: alpha, beta = ab_dev[0], ab_dev[1]
  * read on the device (fade-in coefficient of a captured step graph). */

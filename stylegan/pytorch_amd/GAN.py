@@ -456,73 +456,52 @@ class Discriminator(nn.Module):
             img = self._diffaug_color(img)
         return img
 
-    def _diffaug_color(self, img):
-        """brightness, contrast, lumaflip, hue, saturation: one draw of its own per D evaluation ([B,8]; [B,13] under ADA, columns 8..12
-        the gates), turned into the per-image table {M, t} ONCE, here; the pass, its adjoint, its linear part and the R1 double backward
-        of this evaluation read the table, never p."""
+    def _stage_draws(self, img, nu, ng, u, gu, names=None):
+        """(u, gu) of one stage for one D evaluation: the overrides ``u`` / ``gu`` where set (their widths checked if the stage has
+        ``names`` for them), else fresh uniforms -- [B,nu] draws, or under ADA ONE [B,nu+ng] draw whose columns nu.. are the gates,
+        which the kernels read in place, a row stride apart.  Without ADA gu is None.  torch's graph-safe generator: fresh draws at
+        every replay."""
         B = img.shape[0]
-        u, gu = self.color_override, self.color_gate_override
-        self._override_ok(u, B, 8, "color_override")
+        if names:
+            self._override_ok(u, B, nu, names[0])
         if not self.ada:
-            if u is None:
-                u = torch.rand(B, 8, device=img.device)
-            return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits))
-        self._override_ok(gu, B, 5, "color_gate_override")
+            return (torch.rand(B, nu, device=img.device) if u is None else u), None
+        if names:
+            self._override_ok(gu, B, ng, names[1])
         if u is None or gu is None:
-            r = torch.rand(B, 13, device=img.device)
-            u = r[:, :8] if u is None else u
-            gu = r[:, 8:] if gu is None else gu
-        return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits, gu, self.ada_state))
+            r = torch.rand(B, nu + ng, device=img.device)
+            u = r[:, :nu] if u is None else u
+            gu = r[:, nu:] if gu is None else gu
+        return u, gu
+
+    # The gates are turned into per-image bits (the first five ops) or folded into the per-image table (geometric, colour) ONCE per D
+    # evaluation, here; the adjoint, the linear part and the R1 double backward of this evaluation read the bits or the table, never p.
+    def _diffaug_color(self, img):
+        """brightness, contrast, lumaflip, hue, saturation: [B,8] draws; [B,13] under ADA, columns 8..12 the gates."""
+        u, gu = self._stage_draws(img, 8, 5, self.color_override, self.color_gate_override, ("color_override", "color_gate_override"))
+        return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
 
     def _diffaug_geom(self, img):
-        """scale, rotate, aniso: one draw of its own per D evaluation ([B,5]; [B,8] under ADA, columns 5..7 the gates), turned into the
-        per-image table ONCE, here; the resample, its adjoint and the R1 double backward of this evaluation read the table, never p."""
-        B = img.shape[0]
-        u, gu = self.geom_override, self.geom_gate_override
-        self._override_ok(u, B, 5, "geom_override")
-        if not self.ada:
-            if u is None:
-                u = torch.rand(B, 5, device=img.device)
-            return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits))
-        self._override_ok(gu, B, 3, "geom_gate_override")
-        if u is None or gu is None:
-            r = torch.rand(B, 8, device=img.device)
-            u = r[:, :5] if u is None else u
-            gu = r[:, 5:] if gu is None else gu
-        return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits, gu, self.ada_state))
+        """scale, rotate, aniso: [B,5] draws; [B,8] under ADA, columns 5..7 the gates."""
+        u, gu = self._stage_draws(img, 5, 3, self.geom_override, self.geom_gate_override, ("geom_override", "geom_gate_override"))
+        return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
 
     def _diffaug_pixel(self, img, bits):
-        u = self.diffaug_override
+        """color, translation, cutout: [B,7] draws; [B,10] under ADA, columns 7..9 the gates.  (No width check here: a wrong override
+        is refused by the kernels' wrapper.)"""
         if bits & F.DIFFAUG_BLIT_BITS:
-            return self._diffaug_blit(img, u, bits)
+            return self._diffaug_blit(img, bits)
+        u, gu = self._stage_draws(img, 7, 3, self.diffaug_override, self.ada_gate_override)
         if not self.ada:
-            if u is None:
-                u = torch.rand(img.shape[0], 7, device=img.device)       # torch's graph-safe generator: fresh draws at every replay
             return F.call(F.DiffAugFn, img, u, bits)
-        # ADA: one draw per D evaluation, columns 0..6 the ops' parameters and 7..9 their gates.  The gates are turned into per-image
-        # bits ONCE, here; the adjoint, the linear part and the R1 double backward of this evaluation read the bits, never p.
-        gu = self.ada_gate_override
-        if u is None or gu is None:
-            r = torch.rand(img.shape[0], 10, device=img.device)
-            u = r[:, :7].contiguous() if u is None else u                 # (saved for the backward passes: contiguous once)
-            gu = r[:, 7:] if gu is None else gu
+        if self.diffaug_override is None:
+            u = u.contiguous()                                            # (saved for the backward passes: contiguous once)
         return F.call(F.DiffAugFn, img, u, bits, F.ada_gates(gu, self.ada_state, bits))
 
-    def _diffaug_blit(self, img, u, bits):
-        """A policy with xflip or rot90: nine draws per image, five gates; the kernels read rows of the one [B,14] draw in place."""
-        B = img.shape[0]
-        self._override_ok(u, B, 9, "diffaug_override")
-        if not self.ada:
-            if u is None:
-                u = torch.rand(B, 9, device=img.device)
-            return F.call(F.DiffAugFn, img, u, bits)
-        gu = self.ada_gate_override
-        self._override_ok(gu, B, 5, "ada_gate_override")
-        if u is None or gu is None:
-            r = torch.rand(B, 14, device=img.device)
-            u = r[:, :9] if u is None else u
-            gu = r[:, 9:] if gu is None else gu
-        return F.call(F.DiffAugFn, img, u, bits, F.ada_gates_n(gu, self.ada_state, bits))
+    def _diffaug_blit(self, img, bits):
+        """A policy with xflip or rot90: [B,9] draws; [B,14] under ADA, columns 9..13 the gates."""
+        u, gu = self._stage_draws(img, 9, 5, self.diffaug_override, self.ada_gate_override, ("diffaug_override", "ada_gate_override"))
+        return F.call(F.DiffAugFn, img, u, bits, F.ada_gates_n(gu, self.ada_state, bits) if self.ada else None)
 
     @property
     def ada_p(self):

@@ -8,7 +8,7 @@
 // The pass is one 24 B/pixel stream (one unit per thread, short-lived blocks); every product and sum is rounded to
 // fp32 on its own in the header's order, so a float32 restatement reproduces it bit for bit and the adjoint's coefficients ARE the
 // forward's.  A row equal to (I, 0) is the identity flag: both kernels copy such an image (a block-uniform branch), bit for bit.
-#include "common.h"
+#include "aug.h"
 
 enum { DC_BRIGHTNESS = 256, DC_CONTRAST = 512, DC_LUMAFLIP = 1024, DC_HUE = 2048, DC_SATURATION = 4096,
        DC_OPS = DC_BRIGHTNESS | DC_CONTRAST | DC_LUMAFLIP | DC_HUE | DC_SATURATION };
@@ -138,12 +138,9 @@ __global__ __launch_bounds__(DC_BLOCK) void ada_color_vec_kernel(const float* __
 
 extern "C" int sgx_ada_color_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat,
                                     int B, void* stream) {
-    SGX_REQUIRE(u && mat && B > 0, SGX_EINVAL, "ada_color_matrix: bad arguments (B=%d)", B);
-    SGX_REQUIRE(u_stride >= 8, SGX_EINVAL, "ada_color_matrix: draws %d floats apart, need at least 8", u_stride);
-    SGX_REQUIRE((gu == nullptr) == (state == nullptr), SGX_EINVAL, "ada_color_matrix: gate uniforms and the ADA state come together or not at all");
-    SGX_REQUIRE(!gu || gu_stride >= 5, SGX_EINVAL, "ada_color_matrix: gate uniforms %d floats apart, need at least 5", gu_stride);
-    SGX_REQUIRE(policy_bits >= 0 && (policy_bits & ~DC_OPS) == 0, SGX_EINVAL,
-                "ada_color_matrix: policy bits %d (brightness 256, contrast 512, lumaflip 1024, hue 2048, saturation 4096)", policy_bits);
+    if (int rc = aug_check_matrix("ada_color_matrix", u, u_stride, 8, gu, gu_stride, 5, state, mat, B, policy_bits, DC_OPS,
+                                  "brightness 256, contrast 512, lumaflip 1024, hue 2048, saturation 4096"))
+        return rc;
     SGX_NOTE(0.0, (32.0 + (gu ? 24.0 : 0.0) + 48.0) * B, "ada_color_matrix B%d", B);
     hipLaunchKernelGGL(ada_color_matrix_kernel, dim3((B + DC_BLOCK - 1) / DC_BLOCK), dim3(DC_BLOCK), 0, (hipStream_t)stream, u, u_stride, gu,
                        gu_stride, state, policy_bits, mat, B);
@@ -151,25 +148,30 @@ extern "C" int sgx_ada_color_matrix(const float* u, int u_stride, const float* g
     return 0;
 }
 
-template <bool ADJ, bool BIAS>
-static void dc_launch(bool vec, const float* x, float* y, const float* mat, int B, int HW, hipStream_t st) {
-    if (vec) hipLaunchKernelGGL((ada_color_vec_kernel<ADJ, BIAS>), dim3((HW / 4 + DC_BLOCK - 1) / DC_BLOCK, B), dim3(DC_BLOCK), 0, st, x, y, mat, HW);
-    else hipLaunchKernelGGL((ada_color_px_kernel<ADJ, BIAS>), dim3((HW + DC_BLOCK - 1) / DC_BLOCK, B), dim3(DC_BLOCK), 0, st, x, y, mat, HW);
+// One launch: four pixels (three 16-byte loads and stores) per lane where an IMAGE splits into whole groups of four (H W % 4 == 0: the
+// pass does not know rows) and the bases are aligned, else one.
+int dc_plan(bool ptrs_ok, int B, int H, int W, int adjoint, int with_bias, bool aligned, AugPlan* p) {
+    if (int rc = aug_check_images("ada_color", ptrs_ok, B, H, W)) return rc;
+    SGX_REQUIRE(!(adjoint && with_bias), SGX_EINVAL, "ada_color: the adjoint has no bias");
+    const int HW = H * W, vec = aug_vec4(HW, aligned);
+    *p = AugPlan{1, {{vec ? AUG_K_COLOR_VEC : AUG_K_COLOR_PX, 0, adjoint != 0, 0, with_bias != 0, aug_grid(vec ? HW / 4 : HW), B, 0, 0, HW}}};
+    return 0;
 }
 
 extern "C" int sgx_ada_color(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, int with_bias, void* stream) {
-    SGX_REQUIRE(x && y && mat && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "ada_color: bad arguments (B=%d %dx%d)", B, H, W);
-    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "ada_color: image of %dx%d too large", H, W);
-    SGX_REQUIRE(x != y, SGX_EINVAL, "ada_color: in place is not supported");
-    SGX_REQUIRE(!(adjoint && with_bias), SGX_EINVAL, "ada_color: the adjoint has no bias");
-    const int HW = H * W;
-    // four pixels (three 16-byte loads and stores) per lane where an image splits into whole groups of four and the bases are aligned
-    const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    AugPlan p;
+    if (int rc = dc_plan(x && y && mat, B, H, W, adjoint, with_bias, aug_aligned(x, y), &p)) return rc;
+    if (int rc = aug_check_out_of_place("ada_color", x, y, "")) return rc;
     hipStream_t st = (hipStream_t)stream;
+    const AugLaunch& l = p.l[0];
+    const dim3 grid(l.gx, l.gy), block(DC_BLOCK);
+    const bool vec = l.kernel == AUG_K_COLOR_VEC;
     SGX_NOTE(0.0, 24.0 * B * H * W, "ada_color_%s B%d %dx%d %s", vec ? "vec" : "px", B, H, W, adjoint ? "adj" : with_bias ? "fwd" : "lin");
-    if (adjoint) dc_launch<true, false>(vec, x, y, mat, B, HW, st);
-    else if (with_bias) dc_launch<false, true>(vec, x, y, mat, B, HW, st);
-    else dc_launch<false, false>(vec, x, y, mat, B, HW, st);
+    sgx_by_int<0, 1, 2>(2 * l.mode + l.bias, [&](auto v) {             // linear part, forward, adjoint: <ADJ, BIAS> = <0, 0>, <0, 1>, <1, 0>
+        constexpr bool ADJ = v() == 2, BIAS = v() == 1;
+        if (vec) hipLaunchKernelGGL((ada_color_vec_kernel<ADJ, BIAS>), grid, block, 0, st, x, y, mat, l.HW);
+        else hipLaunchKernelGGL((ada_color_px_kernel<ADJ, BIAS>), grid, block, 0, st, x, y, mat, l.HW);
+    });
     SGX_LAUNCH_CHECK("ada_color");
     return 0;
 }

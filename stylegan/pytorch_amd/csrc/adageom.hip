@@ -8,7 +8,7 @@
 // sgx_ada_geom_matrix turns one D evaluation's draws (and, under ADA, its gate uniforms against p) into the per-image table
 // {T^-1, T} once; the forward, the adjoint and the R1 double backward read the table, never p.  An image with its three ops off gets
 // the exact identity row, which IS its flag: both resample kernels copy such an image (a block-uniform branch).
-#include "common.h"
+#include "aug.h"
 
 enum { DG_SCALE = 32, DG_ROTATE = 64, DG_ANISO = 128, DG_OPS = DG_SCALE | DG_ROTATE | DG_ANISO };
 constexpr int DG_BLOCK = 256;
@@ -209,12 +209,8 @@ __global__ __launch_bounds__(DG_BLOCK) void ada_geom_tile_kernel(const float* __
 
 extern "C" int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat,
                                    int B, void* stream) {
-    SGX_REQUIRE(u && mat && B > 0, SGX_EINVAL, "ada_geom_matrix: bad arguments (B=%d)", B);
-    SGX_REQUIRE(u_stride >= 5, SGX_EINVAL, "ada_geom_matrix: draws %d floats apart, need at least 5", u_stride);
-    SGX_REQUIRE((gu == nullptr) == (state == nullptr), SGX_EINVAL, "ada_geom_matrix: gate uniforms and the ADA state come together or not at all");
-    SGX_REQUIRE(!gu || gu_stride >= 3, SGX_EINVAL, "ada_geom_matrix: gate uniforms %d floats apart, need at least 3", gu_stride);
-    SGX_REQUIRE(policy_bits >= 0 && (policy_bits & ~DG_OPS) == 0, SGX_EINVAL, "ada_geom_matrix: policy bits %d (scale 32, rotate 64, aniso 128)",
-                policy_bits);
+    if (int rc = aug_check_matrix("ada_geom_matrix", u, u_stride, 5, gu, gu_stride, 3, state, mat, B, policy_bits, DG_OPS, "scale 32, rotate 64, aniso 128"))
+        return rc;
     SGX_NOTE(0.0, (20.0 + (gu ? 16.0 : 0.0) + 32.0) * B, "ada_geom_matrix B%d", B);
     hipLaunchKernelGGL(ada_geom_matrix_kernel, dim3((B + DG_BLOCK - 1) / DG_BLOCK), dim3(DG_BLOCK), 0, (hipStream_t)stream, u, u_stride, gu, gu_stride,
                        state, policy_bits, mat, B);
@@ -222,25 +218,30 @@ extern "C" int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu
     return 0;
 }
 
+// One launch: the tile path where an identity image can be copied in 16-byte pieces (rows of whole groups of four, 16-byte aligned
+// bases), else a pixel per thread.
+int dg_plan(bool ptrs_ok, int B, int H, int W, int adjoint, bool aligned, AugPlan* p) {
+    if (int rc = aug_check_images("ada_geom", ptrs_ok, B, H, W)) return rc;
+    const int tiles_x = (W + DG_TILE - 1) / DG_TILE, tiles_y = (H + DG_TILE - 1) / DG_TILE, adj = adjoint != 0;
+    *p = AugPlan{1};
+    if (aug_vec4(W, aligned)) p->l[0] = AugLaunch{AUG_K_GEOM_TILE, 0, adj, 0, 0, tiles_x * tiles_y, B, 0, tiles_x};
+    else p->l[0] = AugLaunch{AUG_K_GEOM_PX, 0, adj, 0, 0, aug_grid((size_t)H * W), B};
+    return 0;
+}
+
 extern "C" int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream) {
-    SGX_REQUIRE(x && y && mat && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "ada_geom: bad arguments (B=%d %dx%d)", B, H, W);
-    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "ada_geom: image of %dx%d too large", H, W);
-    SGX_REQUIRE(x != y, SGX_EINVAL, "ada_geom: in place is not supported (the passes gather)");
+    AugPlan p;
+    if (int rc = dg_plan(x && y && mat, B, H, W, adjoint, aug_aligned(x, y), &p)) return rc;
+    if (int rc = aug_check_out_of_place("ada_geom", x, y, " (the passes gather)")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const char* dir = adjoint ? "adj" : "fwd";
-    // the tile path where an identity image can be copied in 16-byte pieces (rows of whole groups of four, 16-byte aligned bases)
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    if (vec) {
-        const int tiles_x = (W + DG_TILE - 1) / DG_TILE, tiles_y = (H + DG_TILE - 1) / DG_TILE;
-        SGX_NOTE(0.0, 24.0 * B * H * W, "ada_geom_tile B%d %dx%d %s", B, H, W, dir);
-        if (adjoint) hipLaunchKernelGGL((ada_geom_tile_kernel<true>), dim3(tiles_x * tiles_y, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W, tiles_x);
-        else hipLaunchKernelGGL((ada_geom_tile_kernel<false>), dim3(tiles_x * tiles_y, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W, tiles_x);
-    } else {
-        const unsigned gx = (unsigned)(((size_t)H * W + DG_BLOCK - 1) / DG_BLOCK);
-        SGX_NOTE(0.0, 24.0 * B * H * W, "ada_geom_px B%d %dx%d %s", B, H, W, dir);
-        if (adjoint) hipLaunchKernelGGL((ada_geom_px_kernel<true>), dim3(gx, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W);
-        else hipLaunchKernelGGL((ada_geom_px_kernel<false>), dim3(gx, B), dim3(DG_BLOCK), 0, st, x, y, mat, H, W);
-    }
+    const AugLaunch& l = p.l[0];
+    const dim3 grid(l.gx, l.gy), block(DG_BLOCK);
+    const bool tile = l.kernel == AUG_K_GEOM_TILE;
+    SGX_NOTE(0.0, 24.0 * B * H * W, "ada_geom_%s B%d %dx%d %s", tile ? "tile" : "px", B, H, W, adjoint ? "adj" : "fwd");
+    sgx_by_int<0, 1>(l.mode, [&](auto M) {
+        if (tile) hipLaunchKernelGGL((ada_geom_tile_kernel<bool(M())>), grid, block, 0, st, x, y, mat, H, W, l.tiles);
+        else hipLaunchKernelGGL((ada_geom_px_kernel<bool(M())>), grid, block, 0, st, x, y, mat, H, W);
+    });
     SGX_LAUNCH_CHECK("ada_geom");
     return 0;
 }

@@ -18,7 +18,7 @@
 // same order.  A launch without the rot90 bit reads rows (reversed in registers under a flip: diffaug_blit_row_kernel); a launch with
 // it may turn rows into columns for some of its images and stages a square tile through LDS (diffaug_blit_tile_kernel).  What a policy
 // of the first three ops launches (sgx_diffaug, sgx_diffaug_gated) is untouched by it.
-#include "common.h"
+#include "aug.h"
 
 enum { DA_COLOR = 1, DA_TRANSLATION = 2, DA_CUTOUT = 4, DA_XFLIP = 8, DA_ROT90 = 16 };
 enum { DA_OPS3 = DA_COLOR | DA_TRANSLATION | DA_CUTOUT, DA_OPS5 = DA_OPS3 | DA_XFLIP | DA_ROT90 };
@@ -197,58 +197,6 @@ __global__ __launch_bounds__(DA_BLOCK) void diffaug_apply_kernel(const float* __
 #pragma unroll
         for (int k = 0; k < 3 * P; ++k) d[k] = v[k];
     }
-}
-
-static inline int da_nparts(int H, int W) { return (int)(((size_t)H * W + DA_PART_PIXELS - 1) / DA_PART_PIXELS); }
-
-template <int P, bool GATED>
-static void da_launch(const float* x, float* y, const float* u, const int* img_bits, float* part, int B, int H, int W, int policy, int adjoint,
-                      int with_bias, hipStream_t st) {
-    const int nparts = da_nparts(H, W);
-    const char* tag = GATED ? "_gated" : "";
-    if (policy & DA_COLOR) {
-        SGX_NOTE(0.0, 12.0 * B * H * W, "diffaug_sum%s B%d %dx%d %s", tag, B, H, W, adjoint ? "adj" : "fwd");
-        if (adjoint) hipLaunchKernelGGL((diffaug_sum_kernel<P, DA_ADJ, GATED>), dim3(nparts, B), dim3(DA_BLOCK), 0, st, x, u, part, nparts, H, W, policy, img_bits);
-        else hipLaunchKernelGGL((diffaug_sum_kernel<P, DA_PLAIN, GATED>), dim3(nparts, B), dim3(DA_BLOCK), 0, st, x, u, part, nparts, H, W, policy, img_bits);
-    }
-    const unsigned gx = (unsigned)(((size_t)H * (W / P) + DA_BLOCK - 1) / DA_BLOCK);
-    SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug%s B%d %dx%d %s", tag, B, H, W, adjoint ? "adj" : "fwd");
-    if (adjoint) hipLaunchKernelGGL((diffaug_apply_kernel<P, true, GATED>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, (const float*)part, nparts, H, W, policy, with_bias, img_bits);
-    else hipLaunchKernelGGL((diffaug_apply_kernel<P, false, GATED>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, (const float*)part, nparts, H, W, policy, with_bias, img_bits);
-}
-
-extern "C" size_t sgx_diffaug_ws_bytes(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)B * da_nparts(H, W) * sizeof(float);
-}
-
-template <bool GATED>
-static int da_run(const char* name, const float* x, float* y, const float* u, const int* img_bits, int B, int H, int W, int policy_bits, int adjoint,
-                  int with_bias, void* ws, size_t ws_bytes, void* stream) {
-    SGX_REQUIRE(x && y && u && (!GATED || img_bits) && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "%s: bad arguments (B=%d %dx%d)", name, B, H, W);
-    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "%s: image of %dx%d too large", name, H, W);
-    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= DA_OPS3, SGX_EINVAL, "%s: policy bits %d", name, policy_bits);
-    SGX_REQUIRE(x != y, SGX_EINVAL, "%s: in place is not supported (the passes gather)", name);
-    if (policy_bits & DA_COLOR)
-        SGX_REQUIRE(ws && ws_bytes >= sgx_diffaug_ws_bytes(B, H, W), SGX_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes,
-                    sgx_diffaug_ws_bytes(B, H, W));
-    hipStream_t st = (hipStream_t)stream;
-    // four pixels (three 16-byte stores) per lane where rows split into whole groups of four and the bases are 16-byte aligned
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    if (vec) da_launch<4, GATED>(x, y, u, img_bits, (float*)ws, B, H, W, policy_bits, adjoint, with_bias, st);
-    else da_launch<1, GATED>(x, y, u, img_bits, (float*)ws, B, H, W, policy_bits, adjoint, with_bias, st);
-    SGX_LAUNCH_CHECK(name);
-    return 0;
-}
-
-extern "C" int sgx_diffaug(const float* x, float* y, const float* u, int B, int H, int W, int policy_bits, int adjoint, int with_bias,
-                           void* ws, size_t ws_bytes, void* stream) {
-    return da_run<false>("diffaug", x, y, u, nullptr, B, H, W, policy_bits, adjoint, with_bias, ws, ws_bytes, stream);
-}
-
-extern "C" int sgx_diffaug_gated(const float* x, float* y, const float* u, const int* img_bits, int B, int H, int W, int policy_bits, int adjoint,
-                                 int with_bias, void* ws, size_t ws_bytes, void* stream) {
-    return da_run<true>("diffaug_gated", x, y, u, img_bits, B, H, W, policy_bits, adjoint, with_bias, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -515,50 +463,136 @@ __global__ __launch_bounds__(DA_BLOCK) void diffaug_blit_tile_kernel(const float
     da_blit_finish<4, ADJ>(v, ok, q, policy, M, with_bias, y + (((size_t)b * N + i) * N + j0) * 3);
 }
 
-extern "C" int sgx_diffaug_blit(const float* x, float* y, const float* u, int u_stride, const int* img_bits, int B, int H, int W, int policy_bits,
-                                int adjoint, int with_bias, void* ws, size_t ws_bytes, void* stream) {
-    const char* name = "diffaug_blit";
-    SGX_REQUIRE(x && y && u && B > 0 && H > 0 && W > 0 && B <= 65535, SGX_EINVAL, "%s: bad arguments (B=%d %dx%d)", name, B, H, W);
-    SGX_REQUIRE(u_stride >= 9, SGX_EINVAL, "%s: draws %d floats apart, need at least 9", name, u_stride);
-    SGX_REQUIRE((size_t)H * W * 3 < (size_t)1 << 31, SGX_EUNSUPPORTED, "%s: image of %dx%d too large", name, H, W);
-    SGX_REQUIRE(policy_bits >= 0 && policy_bits <= DA_OPS5, SGX_EINVAL, "%s: policy bits %d", name, policy_bits);
-    SGX_REQUIRE(!(policy_bits & DA_ROT90) || H == W, SGX_EINVAL, "%s: rot90 needs square images, got %dx%d", name, H, W);
-    SGX_REQUIRE(x != y, SGX_EINVAL, "%s: in place is not supported (the passes gather)", name);
-    if (policy_bits & DA_COLOR)
-        SGX_REQUIRE(ws && ws_bytes >= sgx_diffaug_ws_bytes(B, H, W), SGX_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, ws_bytes,
-                    sgx_diffaug_ws_bytes(B, H, W));
-    hipStream_t st = (hipStream_t)stream;
-    const int nparts = da_nparts(H, W);
-    float* part = (float*)ws;
-    const char* dir = adjoint ? "adj" : "fwd";
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    if (policy_bits & DA_COLOR) {
-        SGX_NOTE(0.0, 12.0 * B * H * W, "diffaug_blit_sum B%d %dx%d %s", B, H, W, dir);
-        const dim3 grid(nparts, B);
-        if (vec && adjoint) hipLaunchKernelGGL((diffaug_blit_sum_kernel<4, DA_ADJ>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
-        else if (vec) hipLaunchKernelGGL((diffaug_blit_sum_kernel<4, DA_PLAIN>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
-        else if (adjoint) hipLaunchKernelGGL((diffaug_blit_sum_kernel<1, DA_ADJ>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
-        else hipLaunchKernelGGL((diffaug_blit_sum_kernel<1, DA_PLAIN>), grid, dim3(DA_BLOCK), 0, st, x, u, u_stride, part, nparts, H, W, policy_bits, img_bits);
-    }
-    // one apply launch: the tile path wherever an image of the launch may be turned and groups of four are whole and aligned, the row
-    // path (four pixels per lane) without the rot90 bit, the per-pixel path for everything else
-    if (vec && (policy_bits & DA_ROT90)) {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// What a call launches: da_plan decides it, da_run executes it, sgx_aug_plan reports it without launching
+static inline int da_nparts(int H, int W) { return (int)(((size_t)H * W + DA_PART_PIXELS - 1) / DA_PART_PIXELS); }
+
+extern "C" size_t sgx_diffaug_ws_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)B * da_nparts(H, W) * sizeof(float);
+}
+
+static const char* const DA_NAME[] = {"diffaug", "diffaug_gated", "diffaug_blit"};         // by SGX_AUG_PLAN_DIFFAUG / _GATED / _BLIT
+
+// The sum pass if the policy has colour, then one apply launch.  Four pixels (three 16-byte stores) per lane where rows split into
+// whole groups of four and the bases are 16-byte aligned, else one.  A blit call takes the tile path wherever an image of the launch
+// may be turned and groups of four are whole and aligned, the row path (four pixels per lane) without the rot90 bit, the row kernel
+// per pixel for everything else.
+static int da_plan(int entry, bool ptrs_ok, int B, int H, int W, int policy, int adjoint, bool aligned, AugPlan* p) {
+    const char* name = DA_NAME[entry];
+    const bool blit = entry == SGX_AUG_PLAN_BLIT;
+    if (int rc = aug_check_images(name, ptrs_ok, B, H, W)) return rc;
+    SGX_REQUIRE(policy >= 0 && policy <= (blit ? DA_OPS5 : DA_OPS3), SGX_EINVAL, "%s: policy bits %d", name, policy);
+    SGX_REQUIRE(!(policy & DA_ROT90) || H == W, SGX_EINVAL, "%s: rot90 needs square images, got %dx%d", name, H, W);
+    const bool vec = aug_vec4(W, aligned);
+    const int P = vec ? 4 : 1, nparts = da_nparts(H, W), gated = entry == SGX_AUG_PLAN_GATED, adj = adjoint != 0;
+    *p = AugPlan{};
+    if (policy & DA_COLOR) p->l[p->n++] = AugLaunch{blit ? AUG_K_BLIT_SUM : AUG_K_SUM, P, adj ? DA_ADJ : DA_PLAIN, gated, 0, nparts, B, nparts};
+    if (blit && vec && (policy & DA_ROT90)) {
         const int tiles = (W + DA_TILE - 1) / DA_TILE;
-        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_tile B%d %dx%d %s", B, H, W, dir);
-        if (adjoint) hipLaunchKernelGGL((diffaug_blit_tile_kernel<true>), dim3(tiles * tiles, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, W, tiles, policy_bits, with_bias, img_bits);
-        else hipLaunchKernelGGL((diffaug_blit_tile_kernel<false>), dim3(tiles * tiles, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, W, tiles, policy_bits, with_bias, img_bits);
-    } else if (vec) {
-        const unsigned gx = (unsigned)(((size_t)H * (W / 4) + DA_BLOCK - 1) / DA_BLOCK);
-        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_row B%d %dx%d %s", B, H, W, dir);
-        if (adjoint) hipLaunchKernelGGL((diffaug_blit_row_kernel<4, true>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
-        else hipLaunchKernelGGL((diffaug_blit_row_kernel<4, false>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+        p->l[p->n++] = AugLaunch{AUG_K_BLIT_TILE, 0, adj, 0, 0, tiles * tiles, B, nparts, tiles};
     } else {
-        const unsigned gx = (unsigned)(((size_t)H * W + DA_BLOCK - 1) / DA_BLOCK);
-        SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_px B%d %dx%d %s", B, H, W, dir);
-        if (adjoint) hipLaunchKernelGGL((diffaug_blit_row_kernel<1, true>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
-        else hipLaunchKernelGGL((diffaug_blit_row_kernel<1, false>), dim3(gx, B), dim3(DA_BLOCK), 0, st, x, y, u, u_stride, (const float*)part, nparts, H, W, policy_bits, with_bias, img_bits);
+        p->l[p->n++] = AugLaunch{blit ? AUG_K_BLIT_ROW : AUG_K_APPLY, P, adj, gated, 0, aug_grid((size_t)H * (W / P)), B, nparts};
+    }
+    return 0;
+}
+
+// f(P, M, G): a launch's template arguments as integral constants, M of the list Ms
+template <int... Ms, typename F> static void da_by_targs(const AugLaunch& l, F f) {
+    sgx_by_int<1, 4>(l.P, [&](auto p) { sgx_by_int<Ms...>(l.mode, [&](auto m) { sgx_by_int<0, 1>(l.gated, [&](auto g) { f(p, m, g); }); }); });
+}
+
+struct DaCall {
+    const float *x; float* y; const float* u; int u_stride; const int* img_bits;
+    int B, H, W, policy, adjoint, with_bias; void* ws; size_t ws_bytes; void* stream;
+};
+
+static int da_run(int entry, const DaCall& c) {
+    const char* name = DA_NAME[entry];
+    AugPlan p;
+    if (int rc = da_plan(entry, c.x && c.y && c.u && (entry != SGX_AUG_PLAN_GATED || c.img_bits), c.B, c.H, c.W, c.policy, c.adjoint, aug_aligned(c.x, c.y), &p))
+        return rc;
+    SGX_REQUIRE(entry != SGX_AUG_PLAN_BLIT || c.u_stride >= 9, SGX_EINVAL, "%s: draws %d floats apart, need at least 9", name, c.u_stride);
+    if (int rc = aug_check_out_of_place(name, c.x, c.y, " (the passes gather)")) return rc;
+    if (c.policy & DA_COLOR)
+        if (int rc = aug_check_ws(name, c.ws, c.ws_bytes, sgx_diffaug_ws_bytes(c.B, c.H, c.W))) return rc;
+    hipStream_t st = (hipStream_t)c.stream;
+    float* part = (float*)c.ws;
+    const int B = c.B, H = c.H, W = c.W;
+    const char *dir = c.adjoint ? "adj" : "fwd", *tag = entry == SGX_AUG_PLAN_GATED ? "_gated" : "";
+    for (int i = 0; i < p.n; ++i) {
+        const AugLaunch& l = p.l[i];
+        const dim3 grid(l.gx, l.gy), block(DA_BLOCK);
+        switch (l.kernel) {
+        case AUG_K_SUM:
+            SGX_NOTE(0.0, 12.0 * B * H * W, "diffaug_sum%s B%d %dx%d %s", tag, B, H, W, dir);
+            da_by_targs<DA_PLAIN, DA_ADJ>(l, [&](auto P, auto M, auto G) {
+                hipLaunchKernelGGL((diffaug_sum_kernel<P(), M(), bool(G())>), grid, block, 0, st, c.x, c.u, part, l.nparts, H, W, c.policy, c.img_bits);
+            });
+            break;
+        case AUG_K_APPLY:
+            SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug%s B%d %dx%d %s", tag, B, H, W, dir);
+            da_by_targs<0, 1>(l, [&](auto P, auto M, auto G) {
+                hipLaunchKernelGGL((diffaug_apply_kernel<P(), bool(M()), bool(G())>), grid, block, 0, st, c.x, c.y, c.u, (const float*)part, l.nparts, H, W, c.policy,
+                                   c.with_bias, c.img_bits);
+            });
+            break;
+        case AUG_K_BLIT_SUM:
+            SGX_NOTE(0.0, 12.0 * B * H * W, "diffaug_blit_sum B%d %dx%d %s", B, H, W, dir);
+            da_by_targs<DA_PLAIN, DA_ADJ>(l, [&](auto P, auto M, auto) {
+                hipLaunchKernelGGL((diffaug_blit_sum_kernel<P(), M()>), grid, block, 0, st, c.x, c.u, c.u_stride, part, l.nparts, H, W, c.policy, c.img_bits);
+            });
+            break;
+        case AUG_K_BLIT_ROW:
+            SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_%s B%d %dx%d %s", l.P == 4 ? "row" : "px", B, H, W, dir);
+            da_by_targs<0, 1>(l, [&](auto P, auto M, auto) {
+                hipLaunchKernelGGL((diffaug_blit_row_kernel<P(), bool(M())>), grid, block, 0, st, c.x, c.y, c.u, c.u_stride, (const float*)part, l.nparts, H, W,
+                                   c.policy, c.with_bias, c.img_bits);
+            });
+            break;
+        case AUG_K_BLIT_TILE:
+            SGX_NOTE(0.0, 24.0 * B * H * W, "diffaug_blit_tile B%d %dx%d %s", B, H, W, dir);
+            sgx_by_int<0, 1>(l.mode, [&](auto M) {
+                hipLaunchKernelGGL((diffaug_blit_tile_kernel<bool(M())>), grid, block, 0, st, c.x, c.y, c.u, c.u_stride, (const float*)part, l.nparts, W, l.tiles,
+                                   c.policy, c.with_bias, c.img_bits);
+            });
+            break;
+        }
     }
     SGX_LAUNCH_CHECK(name);
+    return 0;
+}
+
+extern "C" int sgx_diffaug(const float* x, float* y, const float* u, int B, int H, int W, int policy_bits, int adjoint, int with_bias,
+                           void* ws, size_t ws_bytes, void* stream) {
+    return da_run(SGX_AUG_PLAN_DIFFAUG, DaCall{x, y, u, 7, nullptr, B, H, W, policy_bits, adjoint, with_bias, ws, ws_bytes, stream});
+}
+
+extern "C" int sgx_diffaug_gated(const float* x, float* y, const float* u, const int* img_bits, int B, int H, int W, int policy_bits, int adjoint,
+                                 int with_bias, void* ws, size_t ws_bytes, void* stream) {
+    return da_run(SGX_AUG_PLAN_GATED, DaCall{x, y, u, 7, img_bits, B, H, W, policy_bits, adjoint, with_bias, ws, ws_bytes, stream});
+}
+
+extern "C" int sgx_diffaug_blit(const float* x, float* y, const float* u, int u_stride, const int* img_bits, int B, int H, int W, int policy_bits,
+                                int adjoint, int with_bias, void* ws, size_t ws_bytes, void* stream) {
+    return da_run(SGX_AUG_PLAN_BLIT, DaCall{x, y, u, u_stride, img_bits, B, H, W, policy_bits, adjoint, with_bias, ws, ws_bytes, stream});
+}
+
+extern "C" int sgx_aug_plan(int entry, int B, int H, int W, int policy_bits, int adjoint, int with_bias, int aligned, int* out) {
+    SGX_REQUIRE(out, SGX_EINVAL, "aug_plan: out is NULL");
+    for (int i = 0; i < SGX_AUG_PLAN_INTS; ++i) out[i] = 0;
+    SGX_REQUIRE(entry >= SGX_AUG_PLAN_DIFFAUG && entry <= SGX_AUG_PLAN_COLOR, SGX_EINVAL, "aug_plan: entry %d", entry);
+    AugPlan p;
+    if (int rc = entry == SGX_AUG_PLAN_GEOM    ? dg_plan(true, B, H, W, adjoint, aligned != 0, &p)
+                 : entry == SGX_AUG_PLAN_COLOR ? dc_plan(true, B, H, W, adjoint, with_bias, aligned != 0, &p)
+                                               : da_plan(entry, true, B, H, W, policy_bits, adjoint, aligned != 0, &p))
+        return rc;
+    out[0] = p.n;
+    for (int i = 0; i < p.n; ++i) {
+        const AugLaunch& l = p.l[i];
+        const int v[] = {l.kernel, l.P, l.mode, l.gated, l.bias, l.gx, l.gy, l.nparts, l.tiles, l.HW};
+        for (int k = 0; k < 10; ++k) out[1 + 10 * i + k] = v[k];
+    }
     return 0;
 }
 

@@ -2466,18 +2466,31 @@ def diffaug_policy_bits(policy):
     return bits
 
 
-def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
+def _rgb_images(x, who):
+    """The images of an augmentation pass: contiguous fp32 [B,H,W,3]."""
     x = _c(x)
     if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
-        raise N.SgxError(f"diffaug: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+        raise N.SgxError(f"{who}: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    return x
+
+
+def _rows(t, width):
+    """Rows of a wider draw (ADA: [B,14], [B,8], [B,13]) are used in place, a row stride apart; anything else is made contiguous."""
+    return t if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= width else _c(t)
+
+
+def _need_gpu(t):
+    """For tensors handed over as ``data_ptr()`` and a row stride, which ``N.ptr`` (contiguous tensors only) cannot check."""
+    if not t.is_cuda:
+        raise N.SgxError("libsgx_hip kernels need GPU tensors (no CPU fallback exists for this path)")
+
+
+def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
+    x = _rgb_images(x, "diffaug")
     B, H, W, _ = x.shape
     blit = bool(bits & DIFFAUG_BLIT_BITS)
     nu = 9 if blit else 7
-    if blit:                                                 # rows of a wider draw (ADA: [B,14]) are used in place, a row stride apart
-        if u.dim() != 2 or u.stride(1) != 1 or u.stride(0) < nu:
-            u = _c(u)
-    else:
-        u = _c(u)
+    u = _rows(u, nu) if blit else _c(u)
     if tuple(u.shape) != (B, nu) or u.dtype != torch.float32 or u.device != x.device:
         raise N.SgxError(f"diffaug: need fp32 [{B},{nu}] draws on {x.device}, got {tuple(u.shape)} {u.dtype} on {u.device}")
     if img_bits is not None and (tuple(img_bits.shape) != (B,) or img_bits.dtype != torch.int32 or img_bits.device != x.device):
@@ -2501,55 +2514,42 @@ def _diffaug(x, u, bits, adjoint, with_bias, img_bits=None):
     return y
 
 
-# The three functions take an optional ``img_bits`` (int32 [B], from ``ada_gates``; no gradient): given, image b is transformed under
-# img_bits[b] (``sgx_diffaug_gated``) and ``bits`` is the union.  It is saved next to ``u`` and handed down the chain, so every pass of
-# one D evaluation -- adjoint, linear part, the R1 double backward -- sees the gates of its forward.
-class DiffAugFn(Function):
-    """y = Mask(Shift(G(L x + b))) with the draws ``u`` [B,7] ([B,9] with a blitting op in ``bits``; G the identity without one; no
-    gradient); backward = the adjoint (DiffAugAdjFn), none when x needs no gradient (the D step's fakes)."""
+def _adjoint_chain(name, run, n_ops, lin=True):
+    """The autograd chain of one image pass ``run(x, adjoint, with_bias, *ops)`` = A x + b, whose ``n_ops`` further operands carry no
+    gradient, defined once:
+        <name>Fn     A x + b   backward = <name>AdjFn; none when x needs no gradient (the D step's fakes)
+        <name>AdjFn  A^T g     backward = <name>LinFn
+        <name>LinFn  A x       backward = <name>AdjFn
+    A Function saves its operands (tensors and None with the graph, integers on the context) and hands them to its backward, so the
+    chain closes under differentiation -- the R1 penalty's double backward runs through it -- and every pass of one D evaluation sees
+    the operands of its forward.  lin=False: the pass has no b, its linear part IS <name>Fn and no <name>LinFn is made."""
+    fns = {}
 
-    @staticmethod
-    def forward(ctx, x, u, bits, img_bits=None):
-        ctx.save_for_backward(u, img_bits)
-        ctx.bits = bits
-        return _diffaug(x, u, bits, False, True, img_bits)
+    def function(kind, adjoint, with_bias, back):
+        def forward(ctx, x, *ops):
+            ops += (None,) * (n_ops - len(ops))
+            ctx.save_for_backward(*[o for o in ops if not isinstance(o, int)])
+            ctx.ints = [(k, o) for k, o in enumerate(ops) if isinstance(o, int)]
+            return run(x, adjoint, with_bias, *ops)
 
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        u, img_bits = ctx.saved_tensors
-        return _bcall(DiffAugAdjFn, g, u, ctx.bits, img_bits), None, None, None
-
-
-class DiffAugAdjFn(Function):
-    """A^T g = L(G^T(Shift^T(Mask g))); backward = A without the bias (DiffAugLinFn)."""
-
-    @staticmethod
-    def forward(ctx, g, u, bits, img_bits=None):
-        ctx.save_for_backward(u, img_bits)
-        ctx.bits = bits
-        return _diffaug(g, u, bits, True, False, img_bits)
-
-    @staticmethod
-    def backward(ctx, gg):
-        u, img_bits = ctx.saved_tensors
-        return _bcall(DiffAugLinFn, gg, u, ctx.bits, img_bits), None, None, None
+        def backward(ctx, g):
+            if kind == "" and not ctx.needs_input_grad[0]:
+                return (None,) * (1 + n_ops)
+            ops = list(ctx.saved_tensors)
+            for k, o in ctx.ints:
+                ops.insert(k, o)
+            return (_bcall(fns[back], g, *ops),) + (None,) * n_ops
+        fns[kind] = type(f"{name}{kind}Fn", (Function,), {"forward": staticmethod(forward), "backward": staticmethod(backward)})
+        return fns[kind]
+    chain = [function("", False, True, "Adj"), function("Adj", True, False, "Lin" if lin else "")]
+    return chain + [function("Lin", False, False, "Adj")] if lin else chain
 
 
-class DiffAugLinFn(Function):
-    """A x = Mask(Shift(G(L x))) (the linear part of DiffAugFn); backward = DiffAugAdjFn."""
-
-    @staticmethod
-    def forward(ctx, x, u, bits, img_bits=None):
-        ctx.save_for_backward(u, img_bits)
-        ctx.bits = bits
-        return _diffaug(x, u, bits, False, False, img_bits)
-
-    @staticmethod
-    def backward(ctx, g):
-        u, img_bits = ctx.saved_tensors
-        return _bcall(DiffAugAdjFn, g, u, ctx.bits, img_bits), None, None, None
+# y = Mask(Shift(G(L x + b))) with the draws ``u`` [B,7] ([B,9] with a blitting op in ``bits``; G the identity without one), its adjoint
+# L(G^T(Shift^T(Mask g))) and its linear part.  Operands (no gradient): ``u``, ``bits`` and an optional ``img_bits`` (int32 [B], from
+# ``ada_gates``): given, image b is transformed under img_bits[b] (``sgx_diffaug_gated``) and ``bits`` is the union.
+DiffAugFn, DiffAugAdjFn, DiffAugLinFn = _adjoint_chain(
+    "DiffAug", lambda x, adjoint, with_bias, u, bits, img_bits: _diffaug(x, u, bits, adjoint, with_bias, img_bits), 3)
 
 
 # ADA (Karras et al., NeurIPS 2020): the gates of one D evaluation and the controller of p, both reading / writing the fp32 [8] state
@@ -2575,10 +2575,9 @@ def ada_gates_n(gu, state, bits):
     policy bit ``1 << g`` -> int32 [B]."""
     if gu.dim() != 2 or gu.shape[1] != 5 or gu.dtype != torch.float32:
         raise N.SgxError(f"ada_gates_n: need fp32 [B,5] uniforms, got {tuple(gu.shape)} {gu.dtype}")
-    if gu.stride(1) != 1 or gu.stride(0) < 5:
-        gu = _c(gu)
+    gu = _rows(gu, 5)
     _ada_state_ok(state, gu.device, "ada_gates_n")
-    N.ptr(state)                                             # (refuses CPU tensors: gu is on the state's device)
+    _need_gpu(gu)
     out = torch.empty(gu.shape[0], dtype=torch.int32, device=gu.device)
     N.check(N.lib().sgx_ada_gates_n(gu.data_ptr(), gu.stride(0), 5, N.ptr(state), int(bits), N.ptr(out), gu.shape[0], N.stream()),
             "sgx_ada_gates_n")
@@ -2597,162 +2596,74 @@ def ada_update(real_logits, state, target, adjust_per_image, interval):
     return state
 
 
+# The two op groups that are one table of per-image affine maps per D evaluation and one pass under it: per image the draws, the gate
+# uniforms and the floats of a table row, the group's policy bits, the library's entry point.
+_ADA_MATRIX = {"geom": (5, 3, 8, DIFFAUG_GEOM_MASK, "sgx_ada_geom_matrix"), "color": (8, 5, 12, DIFFAUG_COLOR_MASK, "sgx_ada_color_matrix")}
+
+
+def _ada_matrix(group, u, bits, gu, state):
+    nu, ng, nm, mask, entry = _ADA_MATRIX[group]
+    who = f"ada_{group}_matrix"
+    if u.dim() != 2 or u.shape[1] != nu or u.dtype != torch.float32:
+        raise N.SgxError(f"{who}: need fp32 [B,{nu}] draws, got {tuple(u.shape)} {u.dtype}")
+    u = _rows(u, nu)
+    if (gu is None) != (state is None):
+        raise N.SgxError(f"{who}: gate uniforms and the ADA state come together or not at all")
+    B = u.shape[0]
+    gp, gs = None, 0
+    if gu is not None:
+        if tuple(gu.shape) != (B, ng) or gu.dtype != torch.float32 or gu.device != u.device:
+            raise N.SgxError(f"{who}: need fp32 [{B},{ng}] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
+        gu = _rows(gu, ng)
+        _ada_state_ok(state, u.device, who)
+        gp, gs = gu.data_ptr(), gu.stride(0)
+    _need_gpu(u)
+    mat = torch.empty(B, nm, dtype=torch.float32, device=u.device)
+    N.check(getattr(N.lib(), entry)(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & mask, N.ptr(mat), B, N.stream()), entry)
+    return mat
+
+
+def _ada_table_pass(who, width, x, mat):
+    x = _rgb_images(x, who)
+    if tuple(mat.shape) != (x.shape[0], width) or mat.dtype != torch.float32 or mat.device != x.device:
+        raise N.SgxError(f"{who}: need an fp32 [{x.shape[0]},{width}] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
+    return x, _c(mat), torch.empty_like(x)
+
+
 # The general geometric group of the ADA paper (scale, rotate, aniso; ``sgx_ada_geom_matrix`` / ``sgx_ada_geom``, include/sgx.h): one
-# table of per-image affine maps per D evaluation and one bilinear resample R.  R is linear, so AdaGeomFn (R x) and AdaGeomAdjFn (R^T g)
-# are each other's backward: the pair closes under differentiation and the R1 double backward runs through it.  Both save only the table.
+# bilinear resample R under the table.  R is linear, so AdaGeomFn (R x) and AdaGeomAdjFn (R^T g) are each other's backward.
 def ada_geom_matrix(u, bits, gu=None, state=None):
     """u fp32 [B,5] draws (rows of a wider draw are read in place) -> the fp32 [B,8] table {T^-1, T} of the geometric ops in ``bits``
     (32 scale, 64 rotate, 128 aniso); with ``gu`` fp32 [B,3] gate uniforms and the ADA ``state``, an op is on for image b iff
     gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0,1, 1,0,0,1)."""
-    if u.dim() != 2 or u.shape[1] != 5 or u.dtype != torch.float32:
-        raise N.SgxError(f"ada_geom_matrix: need fp32 [B,5] draws, got {tuple(u.shape)} {u.dtype}")
-    if u.stride(1) != 1 or u.stride(0) < 5:
-        u = _c(u)
-    if (gu is None) != (state is None):
-        raise N.SgxError("ada_geom_matrix: gate uniforms and the ADA state come together or not at all")
-    B = u.shape[0]
-    gp, gs = None, 0
-    if gu is not None:
-        if tuple(gu.shape) != (B, 3) or gu.dtype != torch.float32 or gu.device != u.device:
-            raise N.SgxError(f"ada_geom_matrix: need fp32 [{B},3] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
-        if gu.stride(1) != 1 or gu.stride(0) < 3:
-            gu = _c(gu)
-        _ada_state_ok(state, u.device, "ada_geom_matrix")
-        gp, gs = gu.data_ptr(), gu.stride(0)
-    if not u.is_cuda:
-        raise N.SgxError("libsgx_hip kernels need GPU tensors (no CPU fallback exists for this path)")
-    mat =torch.empty(B, 8, dtype=torch.float32, device=u.device)
-    N.check(N.lib().sgx_ada_geom_matrix(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_GEOM_MASK, N.ptr(mat), B,
-                                        N.stream()), "sgx_ada_geom_matrix")
-    return mat
+    return _ada_matrix("geom", u, bits, gu, state)
 
 
 def _ada_geom(x, mat, adjoint):
-    x = _c(x)
-    if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
-        raise N.SgxError(f"ada_geom: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    x, mat, y = _ada_table_pass("ada_geom", 8, x, mat)
     B, H, W, _ = x.shape
-    if tuple(mat.shape) != (B, 8) or mat.dtype != torch.float32 or mat.device != x.device:
-        raise N.SgxError(f"ada_geom: need an fp32 [{B},8] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
-    y = torch.empty_like(x)
-    N.check(N.lib().sgx_ada_geom(N.ptr(x), N.ptr(y), N.ptr(_c(mat)), B, H, W, int(adjoint), N.stream()), "sgx_ada_geom")
+    N.check(N.lib().sgx_ada_geom(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), N.stream()), "sgx_ada_geom")
     return y
 
 
-class AdaGeomFn(Function):
-    """y = R x, the bilinear resample under the table ``mat`` (no gradient); backward = the adjoint (AdaGeomAdjFn), none when x needs
-    no gradient (the D step's fakes)."""
-
-    @staticmethod
-    def forward(ctx, x, mat):
-        ctx.save_for_backward(mat)
-        return _ada_geom(x, mat, False)
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        mat, = ctx.saved_tensors
-        return _bcall(AdaGeomAdjFn, g, mat), None
-
-
-class AdaGeomAdjFn(Function):
-    """z = R^T g; backward = R (AdaGeomFn)."""
-
-    @staticmethod
-    def forward(ctx, g, mat):
-        ctx.save_for_backward(mat)
-        return _ada_geom(g, mat, True)
-
-    @staticmethod
-    def backward(ctx, gg):
-        mat, = ctx.saved_tensors
-        return _bcall(AdaGeomFn, gg, mat), None
+AdaGeomFn, AdaGeomAdjFn = _adjoint_chain("AdaGeom", lambda x, adjoint, with_bias, mat: _ada_geom(x, mat, adjoint), 1, lin=False)
 
 
 # The colour group of the ADA paper (brightness, contrast, lumaflip, hue, saturation; ``sgx_ada_color_matrix`` / ``sgx_ada_color``,
-# include/sgx.h): one table of per-image affine maps {M, t} of the RGB vector per D evaluation and one streaming pass.  The chain
-# AdaColorFn (M x + t) -> AdaColorAdjFn (M^T g) -> AdaColorLinFn (M x) -> AdaColorAdjFn closes under differentiation, so the R1 double
-# backward runs through it.  All three save only the table.
+# include/sgx.h): one streaming pass y = M x + t per pixel under the table {M, t}; AdaColorAdjFn is M^T g, AdaColorLinFn M x.
 def ada_color_matrix(u, bits, gu=None, state=None):
     """u fp32 [B,8] draws (rows of a wider draw are read in place) -> the fp32 [B,12] table {M row major, t} of the colour ops in ``bits``
     (256 brightness, 512 contrast, 1024 lumaflip, 2048 hue, 4096 saturation); with ``gu`` fp32 [B,5] gate uniforms and the ADA ``state``,
     an op is on for image b iff gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0, 0,1,0, 0,0,1, 0,0,0)."""
-    if u.dim() != 2 or u.shape[1] != 8 or u.dtype != torch.float32:
-        raise N.SgxError(f"ada_color_matrix: need fp32 [B,8] draws, got {tuple(u.shape)} {u.dtype}")
-    if u.stride(1) != 1 or u.stride(0) < 8:
-        u = _c(u)
-    if (gu is None) != (state is None):
-        raise N.SgxError("ada_color_matrix: gate uniforms and the ADA state come together or not at all")
-    B = u.shape[0]
-    gp, gs = None, 0
-    if gu is not None:
-        if tuple(gu.shape) != (B, 5) or gu.dtype != torch.float32 or gu.device != u.device:
-            raise N.SgxError(f"ada_color_matrix: need fp32 [{B},5] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
-        if gu.stride(1) != 1 or gu.stride(0) < 5:
-            gu = _c(gu)
-        _ada_state_ok(state, u.device, "ada_color_matrix")
-        gp, gs = gu.data_ptr(), gu.stride(0)
-    if not u.is_cuda:
-        raise N.SgxError("libsgx_hip kernels need GPU tensors (no CPU fallback exists for this path)")
-    mat = torch.empty(B, 12, dtype=torch.float32, device=u.device)
-    N.check(N.lib().sgx_ada_color_matrix(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_COLOR_MASK, N.ptr(mat), B,
-                                         N.stream()), "sgx_ada_color_matrix")
-    return mat
+    return _ada_matrix("color", u, bits, gu, state)
 
 
 def _ada_color(x, mat, adjoint, with_bias):
-    x = _c(x)
-    if x.dim() != 4 or x.shape[3] != 3 or x.dtype != torch.float32:
-        raise N.SgxError(f"ada_color: need fp32 [B,H,W,3] images, got {tuple(x.shape)} {x.dtype}")
+    x, mat, y = _ada_table_pass("ada_color", 12, x, mat)
     B, H, W, _ = x.shape
-    if tuple(mat.shape) != (B, 12) or mat.dtype != torch.float32 or mat.device != x.device:
-        raise N.SgxError(f"ada_color: need an fp32 [{B},12] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
-    y = torch.empty_like(x)
-    N.check(N.lib().sgx_ada_color(N.ptr(x), N.ptr(y), N.ptr(_c(mat)), B, H, W, int(adjoint), int(with_bias), N.stream()), "sgx_ada_color")
+    N.check(N.lib().sgx_ada_color(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), int(with_bias), N.stream()), "sgx_ada_color")
     return y
 
 
-class AdaColorFn(Function):
-    """y = M x + t per pixel under the table ``mat`` (no gradient); backward = the adjoint (AdaColorAdjFn), none when x needs no
-    gradient (the D step's fakes)."""
-
-    @staticmethod
-    def forward(ctx, x, mat):
-        ctx.save_for_backward(mat)
-        return _ada_color(x, mat, False, True)
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        mat, = ctx.saved_tensors
-        return _bcall(AdaColorAdjFn, g, mat), None
-
-
-class AdaColorAdjFn(Function):
-    """z = M^T g; backward = M without the bias (AdaColorLinFn)."""
-
-    @staticmethod
-    def forward(ctx, g, mat):
-        ctx.save_for_backward(mat)
-        return _ada_color(g, mat, True, False)
-
-    @staticmethod
-    def backward(ctx, gg):
-        mat, = ctx.saved_tensors
-        return _bcall(AdaColorLinFn, gg, mat), None
-
-
-class AdaColorLinFn(Function):
-    """M x (the linear part of AdaColorFn); backward = AdaColorAdjFn."""
-
-    @staticmethod
-    def forward(ctx, x, mat):
-        ctx.save_for_backward(mat)
-        return _ada_color(x, mat, False, False)
-
-    @staticmethod
-    def backward(ctx, g):
-        mat, = ctx.saved_tensors
-        return _bcall(AdaColorAdjFn, g, mat), None
+AdaColorFn, AdaColorAdjFn, AdaColorLinFn = _adjoint_chain(
+    "AdaColor", lambda x, adjoint, with_bias, mat: _ada_color(x, mat, adjoint, with_bias), 1)

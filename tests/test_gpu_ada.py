@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import ada_ref as A
+import aug_ref as AR
 import diffaug_ref as R
 import golden_util as gu
 from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
@@ -57,7 +58,8 @@ SENTINEL = 12345.5
 
 
 def run_gated(xd, ud, bitsd, adjoint, with_bias, policy=7):
-    """sgx_diffaug_gated into a buffer with guard floats on both sides of y; -> y (a copy), the guards checked."""
+    """sgx_diffaug_gated into a buffer with guard floats on both sides of y; -> y (a copy), the guards checked, and every launch the
+    profiler recorded what sgx_aug_plan reports for the call."""
     from stylegan.pytorch_amd import native as N
     B, H, W, _ = xd.shape
     n = xd.numel()
@@ -66,9 +68,14 @@ def run_gated(xd, ud, bitsd, adjoint, with_bias, policy=7):
     L = N.lib()
     nb = L.sgx_diffaug_ws_bytes(B, H, W)
     ws = N.workspace(nb, xd.device)
-    N.check(L.sgx_diffaug_gated(N.ptr(xd), N.ptr(y), N.ptr(ud), N.ptr(bitsd), B, H, W, policy, int(adjoint), int(with_bias), N.ptr(ws), nb,
-                                N.stream()), "sgx_diffaug_gated")
-    torch.cuda.synchronize()
+    N.prof_start(1)
+    try:
+        rc = L.sgx_diffaug_gated(N.ptr(xd), N.ptr(y), N.ptr(ud), N.ptr(bitsd), B, H, W, policy, int(adjoint), int(with_bias), N.ptr(ws), nb, N.stream())
+        torch.cuda.synchronize()
+    finally:
+        N.prof_start(0)
+    N.check(rc, "sgx_diffaug_gated")
+    AR.assert_recorded_is_planned(N, AR.GATED, xd, y, policy, adjoint, with_bias)
     assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all()), "guard floats were written"
     return y.clone()
 

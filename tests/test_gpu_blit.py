@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ada_ref as A
+import aug_ref as AR
 import blit_cases as C
 import blit_ref as Bl
 import golden_util as gu
@@ -54,6 +55,7 @@ def run_blit(xd, ud, bitsd, policy, adjoint, with_bias):
         N.prof_start(0)
     notes = [r[4].split(" ")[0] for r in N.prof_records()]
     N.check(rc, "sgx_diffaug_blit")
+    AR.assert_recorded_is_planned(N, AR.BLIT, xd, y, policy, adjoint, with_bias)        # kernels, template arguments, grids: sgx_aug_plan's
     assert bool((buf[:GUARD + off] == SENTINEL).all()) and bool((buf[GUARD + off + n:] == SENTINEL).all()), "guard floats were written"
     return y.clone(), notes
 

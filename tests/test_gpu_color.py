@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import ada_ref as A
+import aug_ref as AR
 import blit_ref as Bl
 import color_cases as CC
 import color_ref as K
@@ -68,6 +69,7 @@ def run_color(xd, matd, adjoint, with_bias):
         N.prof_start(0)
     notes = [r[4].split(" ")[0] for r in N.prof_records()]
     N.check(rc, "sgx_ada_color")
+    AR.assert_recorded_is_planned(N, AR.COLOR, xd, y, 0, adjoint, with_bias)            # kernel, template arguments, grid: sgx_aug_plan's
     assert bool((buf[:GUARD + off] == SENTINEL).all()) and bool((buf[GUARD + off + n:] == SENTINEL).all()), "guard floats were written"
     return y.clone(), notes
 
@@ -252,6 +254,7 @@ def recorded(fn):
         torch.cuda.synchronize()
     finally:
         N.prof_start(0)
+    AR.assert_records_are_planned(N)                                        # every image-pass launch: a launch sgx_aug_plan reports for its call
     return out, [r[4].split(" ")[0] for r in N.prof_records()]
 
 

@@ -6,6 +6,7 @@ import random
 import pytest
 import torch
 
+import aug_ref as AR
 import diffaug_ref as R
 import golden_util as gu
 from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
@@ -18,8 +19,16 @@ OPT = dict(learning_rate=0.003, beta_1=0, beta_2=0.99, eps=1e-8)
 
 
 def run_kernel(x, u, bits, adjoint, with_bias):
-    from stylegan.pytorch_amd import functional as F
-    return F._diffaug(x, u, bits, adjoint, with_bias)
+    """functional._diffaug (sgx_diffaug) under the library's profiler: every launch it records is what sgx_aug_plan reports for the call."""
+    from stylegan.pytorch_amd import functional as F, native as N
+    N.prof_start(1)
+    try:
+        y = F._diffaug(x, u, bits, adjoint, with_bias)
+        torch.cuda.synchronize()
+    finally:
+        N.prof_start(0)
+    AR.assert_recorded_is_planned(N, AR.DIFFAUG, x, y, bits, adjoint, with_bias)
+    return y
 
 
 # (B, H, W, base offset in floats): the vector path (W % 4 == 0, aligned bases) and the per-pixel one (odd widths, unaligned base)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ada_ref as A
+import aug_ref as AR
 import blit_ref as Bl
 import geom_cases as GC
 import geom_ref as G
@@ -63,6 +64,7 @@ def run_geom(xd, matd, adjoint):
         N.prof_start(0)
     notes = [r[4].split(" ")[0] for r in N.prof_records()]
     N.check(rc, "sgx_ada_geom")
+    AR.assert_recorded_is_planned(N, AR.GEOM, xd, y, 0, adjoint)                        # kernel, template argument, grid: sgx_aug_plan's
     assert bool((buf[:GUARD + off] == SENTINEL).all()) and bool((buf[GUARD + off + n:] == SENTINEL).all()), "guard floats were written"
     return y.clone(), notes
 
@@ -301,6 +303,7 @@ def recorded(fn):
         torch.cuda.synchronize()
     finally:
         N.prof_start(0)
+    AR.assert_records_are_planned(N)                                        # every image-pass launch: a launch sgx_aug_plan reports for its call
     return out, [r[4].split(" ")[0] for r in N.prof_records()]
 
 
