@@ -390,6 +390,56 @@ int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W
 int sgx_ada_color_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
                          void* stream);
 int sgx_ada_color(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, int with_bias, void* stream);
+/* Image-space filtering, the fourth augmentation group of the ADA paper: policy bit 8192 = imgfilter, applied AFTER the colour ops
+ * above (last in the canonical order) to fp32 [B][H][W][3] images; pixels that the earlier stages zeroed are filtered like any others.
+ * The filter bank is constant, 4 bands x 43 taps, built once in fp64 on the host:
+ *   lo = [(1 - sqrt 3), (3 - sqrt 3), (3 + sqrt 3), (1 + sqrt 3)] / (4 sqrt 2)  (the sym2 low-pass),  hi[k] = lo[k] (-1)^k,
+ *   lo2 = (lo * reverse(lo)) / 2,  hi2 = (hi * reverse(hi)) / 2  (7 taps each);  fb starts as the 4 x 1 column (1,0,0,0)^T; for i = 1, 2, 3:
+ *   zero-stuff every row (length n -> 2 n - 1), convolve every row with lo2, add hi2 to the centre seven taps of row i (row lengths
+ *   1 -> 7 -> 19 -> 43); taps with |v| < 1e-12 are set to exactly 0.  Every row is symmetric about tap 21, the rows have 37, 37, 15 and
+ *   5 non-zero taps, the four rows sum to the unit impulse at tap 21, fb[0] sums to 1 and the other rows to 0.  The kernels hold the
+ *   rows rounded to fp32 as half-rows fbh[4][22], fbh[i][j] = fb[i][21 + j]: the symmetry is structural.
+ * u: DEVICE fp32, row b at u + b * u_stride (u_stride >= 8), eight uniforms in [0,1); with the variate of the groups above,
+ * z(ua, ub) = clamp(sqrt(-2 ln(1 - ua)) cos(2 pi ub), -3, 3), the band gains start from g = (1,1,1,1) and for band i = 0..3 in order:
+ *   t = (1,1,1,1);  t[i] = 2^z(u[2i], u[2i+1]) when the band is on for the image, else 1;  t <- t / sqrt(mean(t^2));  g <- g t elementwise
+ * (the paper's power-preserving normalisation with imgfilter_std = 1 and band strengths (1,1,1,1); fp32: n = sqrt(0.25 (3 + t_i t_i)),
+ * g_k <- g_k * ((k == i ? t_i : 1) / n), every product, sum and quotient rounded on its own, the precise logf / cosf / exp2f / sqrtf; a
+ * band that is off gives n = 1 and t = (1,1,1,1) exactly).  Band i is on when imgfilter is in policy_bits and either gu == NULL (all four
+ * on) or its gate uniform is strictly below p = state[0] read on the device: gu row b at gu + b * gu_stride (gu_stride >= 4), columns
+ * 0..3 gating the bands on their own, as the paper does; gu and state are both given or both NULL.
+ * sgx_ada_filter_matrix: one launch writes the half-row c[j] = ((g_0 fbh[0][j] + g_1 fbh[1][j]) + g_2 fbh[2][j]) + g_3 fbh[3][j],
+ *   j = 0..21, of every image, fp32 [B][22]; the filter is h[k] = c[|k - 21|].  An image whose four bands are all off (and every image
+ *   when policy_bits lacks 8192) gets (1, 0, ..., 0) by a branch, not by the sum:
+ *   that row is the identity flag -- the passes copy such an image bit for bit.  Made once per D evaluation; the forward, the adjoint
+ *   and the R1 double backward read the table, never p.
+ * sgx_ada_filter: per image and per channel y = A_v A_h x, along an axis of length N
+ *     (A x)[i] = sum_{k = 0..42} h[k] x[refl_N(i + k - 21)],
+ *   refl whole-sample reflection continued periodically: with P = 2 (N - 1) and m = q mod P (non-negative), refl = m if m < N, else
+ *   P - m -- np.pad(mode="reflect") for any pad width; defined for N >= 2, so H < 2 or W < 2 is refused.  At N >= 22 a sample has at
+ *   most 3 padded positions folding onto it, at N = 4 it has 15, at N = 2 it has 22.
+ *   adjoint = 1:  y = A_h^T A_v^T x as a gather, no atomics:
+ *     (A^T g)[j] = sum_{q in [-21, N + 20], refl(q) = j} sum_{i in [0, N)} h[q - i + 21] g[i],   h = 0 outside 0..42.
+ *   The op has no bias, so its linear part is itself.  Every output of one axis is computed as
+ *     acc = c[0] v(0);  acc = fma(c[j], v(+j) + v(-j), acc) for j = 1..21   (fp32, the sum rounded, then one fused multiply-add)
+ *   with v(d) = x[refl(i + d)] in the forward and, in the adjoint, the zero-extended g at q + d, the q of one j summed in ascending
+ *   order -- by every kernel, so the launch paths agree bit for bit.  One axis per launch: the forward filters along W into the
+ *   workspace and then along H, the adjoint along H and then along W.  ws: sgx_ada_filter_workspace_bytes(B, H, W) = 12 B H W bytes
+ *   (the image between the two axes), 16-byte aligned, apart from x and y; x != y.  With W % 4 == 0, 16-byte aligned x and y and
+ *   H, W >= 44 a block stages a tile (16 rows x 64 pixels, or 64 rows x 64 floats) and its 21-sample halo through LDS, the reflection
+ *   applied while staging, and a lane filters four consecutive outputs; else one output float per thread, any number of reflections.
+ *   An image whose row compares equal to the identity row is copied instead, bit for bit (-0, infinities and NaN payloads included).
+ * sgx_ada_filter_plan: host-only, what sgx_ada_filter will launch (the entry executes the same plan).  aligned: x and y are 16-byte
+ *   aligned.  out[SGX_ADA_FILTER_PLAN_INTS]: [0] the number of launches (2), then six ints per launch, in launch order: the kernel
+ *   (0 ada_filter_px_kernel<AXIS, ADJ>, 1 ada_filter_tile_kernel<AXIS, ADJ>), AXIS (0 along W, 1 along H), ADJ, grid x, grid y (= B),
+ *   tiles per row of tiles (0 for the general kernel); every block is 256 threads, no launch has dynamic LDS.  Returns 0, or what the
+ *   entry returns for these arguments (SGX_EINVAL: B outside 1..65535, H or W < 2, a NULL out; SGX_EUNSUPPORTED: 3 H W >= 2^31); out is
+ *   zeroed on every error but a NULL out. */
+int sgx_ada_filter_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
+                          void* stream);
+size_t sgx_ada_filter_workspace_bytes(int B, int H, int W);
+int sgx_ada_filter(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* ws, size_t ws_bytes, void* stream);
+#define SGX_ADA_FILTER_PLAN_INTS 13
+int sgx_ada_filter_plan(int B, int H, int W, int adjoint, int aligned, int* out);
 /* Host-only query: what the image pass `entry` (SGX_AUG_PLAN_DIFFAUG / _GATED / _BLIT / _GEOM / _COLOR for sgx_diffaug / sgx_diffaug_gated /
  * sgx_diffaug_blit / sgx_ada_geom / sgx_ada_color) will launch for B images of H x W.  The entry points execute the same plan.  aligned:
  * both image bases are 16-byte aligned.  policy_bits is read for the first three entries only, with_bias for the colour pass only.

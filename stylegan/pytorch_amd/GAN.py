@@ -356,7 +356,7 @@ class Discriminator(nn.Module):
                  ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
-        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation' ('' = off); parsed here
+        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation,imgfilter' ('' = off); parsed here
         # so that a bad policy fails at construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
@@ -445,15 +445,21 @@ class Discriminator(nn.Module):
     color_override = None
     color_gate_override = None
 
+    # and for the image-space filter (imgfilter): its [B,8] draws and, under ADA, its [B,4] gate uniforms (one per band)
+    filter_override = None
+    filter_gate_override = None
+
     def _diffaug(self, img):
         """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage,
-        then the colour stage."""
+        then the colour stage, then the image-space filter."""
         if self._diffaug_bits & F.DIFFAUG_PIXEL_MASK:
             img = self._diffaug_pixel(img, self._diffaug_bits & F.DIFFAUG_PIXEL_MASK)
         if self._diffaug_bits & F.DIFFAUG_GEOM_MASK:
             img = self._diffaug_geom(img)
         if self._diffaug_bits & F.DIFFAUG_COLOR_MASK:
             img = self._diffaug_color(img)
+        if self._diffaug_bits & F.DIFFAUG_FILTER_MASK:
+            img = self._diffaug_filter(img)
         return img
 
     def _stage_draws(self, img, nu, ng, u, gu, names=None):
@@ -480,6 +486,11 @@ class Discriminator(nn.Module):
         """brightness, contrast, lumaflip, hue, saturation: [B,8] draws; [B,13] under ADA, columns 8..12 the gates."""
         u, gu = self._stage_draws(img, 8, 5, self.color_override, self.color_gate_override, ("color_override", "color_gate_override"))
         return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
+
+    def _diffaug_filter(self, img):
+        """imgfilter: [B,8] draws; [B,12] under ADA, columns 8..11 the gates of the four bands."""
+        u, gu = self._stage_draws(img, 8, 4, self.filter_override, self.filter_gate_override, ("filter_override", "filter_gate_override"))
+        return F.call(F.AdaFilterFn, img, F.ada_filter_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
 
     def _diffaug_geom(self, img):
         """scale, rotate, aniso: [B,5] draws; [B,8] under ADA, columns 5..7 the gates."""
@@ -1013,7 +1024,9 @@ class StyleGAN:
                None if self.dis.geom_override is None else self.dis.geom_override.data_ptr(),
                None if not self._ada_on() or self.dis.geom_gate_override is None else self.dis.geom_gate_override.data_ptr(),
                None if self.dis.color_override is None else self.dis.color_override.data_ptr(),
-               None if not self._ada_on() or self.dis.color_gate_override is None else self.dis.color_gate_override.data_ptr())
+               None if not self._ada_on() or self.dis.color_gate_override is None else self.dis.color_gate_override.data_ptr(),
+               None if self.dis.filter_override is None else self.dis.filter_override.data_ptr(),
+               None if not self._ada_on() or self.dis.filter_gate_override is None else self.dis.filter_gate_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)

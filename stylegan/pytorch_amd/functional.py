@@ -2442,18 +2442,22 @@ DIFFAUG_PIXEL_MASK = 31                                                      # t
 DIFFAUG_COLOR_OPS = ("brightness", "contrast", "lumaflip", "hue", "saturation")
 DIFFAUG_COLOR_BITS = {"brightness": 256, "contrast": 512, "lumaflip": 1024, "hue": 2048, "saturation": 4096}
 DIFFAUG_COLOR_MASK = 256 | 512 | 1024 | 2048 | 4096
+# the image-space filtering group of the ADA paper, applied after the colour group by its own kernels (``sgx_ada_filter``, further down)
+DIFFAUG_FILTER_OPS = ("imgfilter",)
+DIFFAUG_FILTER_BITS = {"imgfilter": 8192}
+DIFFAUG_FILTER_MASK = 8192
 
 
 def diffaug_policy_bits(policy):
     """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout,scale,rotate,aniso,
-    brightness,contrast,lumaflip,hue,saturation`` in that (canonical) order, each at most once; '' or None: no augmentation.  Anything
+    brightness,contrast,lumaflip,hue,saturation,imgfilter`` in that (canonical) order, each at most once; '' or None: no augmentation.  Anything
     else raises ValueError."""
     if policy is None:
         return 0
     if not isinstance(policy, str):
         raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
-    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS
-    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS}
+    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS + DIFFAUG_FILTER_OPS
+    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS, **DIFFAUG_FILTER_BITS}
     bits, last = 0, -1
     for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
         if name not in order:
@@ -2596,9 +2600,10 @@ def ada_update(real_logits, state, target, adjust_per_image, interval):
     return state
 
 
-# The two op groups that are one table of per-image affine maps per D evaluation and one pass under it: per image the draws, the gate
-# uniforms and the floats of a table row, the group's policy bits, the library's entry point.
-_ADA_MATRIX = {"geom": (5, 3, 8, DIFFAUG_GEOM_MASK, "sgx_ada_geom_matrix"), "color": (8, 5, 12, DIFFAUG_COLOR_MASK, "sgx_ada_color_matrix")}
+# The three op groups that are one per-image table per D evaluation and one pass under it: per image the draws, the gate uniforms and
+# the floats of a table row, the group's policy bits, the library's entry point.
+_ADA_MATRIX = {"geom": (5, 3, 8, DIFFAUG_GEOM_MASK, "sgx_ada_geom_matrix"), "color": (8, 5, 12, DIFFAUG_COLOR_MASK, "sgx_ada_color_matrix"),
+               "filter": (8, 4, 22, DIFFAUG_FILTER_MASK, "sgx_ada_filter_matrix")}
 
 
 def _ada_matrix(group, u, bits, gu, state):
@@ -2667,3 +2672,26 @@ def _ada_color(x, mat, adjoint, with_bias):
 
 AdaColorFn, AdaColorAdjFn, AdaColorLinFn = _adjoint_chain(
     "AdaColor", lambda x, adjoint, with_bias, mat: _ada_color(x, mat, adjoint, with_bias), 1)
+
+
+# The image-space filtering group of the ADA paper (imgfilter; ``sgx_ada_filter_matrix`` / ``sgx_ada_filter``, include/sgx.h): one
+# symmetric 43-tap filter per image, applied separably with reflection, y = A_v A_h x.  The op is linear, so AdaFilterFn (A x) and
+# AdaFilterAdjFn (A^T g) are each other's backward.
+def ada_filter_matrix(u, bits, gu=None, state=None):
+    """u fp32 [B,8] draws (rows of a wider draw are read in place) -> the fp32 [B,22] table of half-rows c (the filter is
+    h[k] = c[|k - 21|]) when ``bits`` has 8192 (imgfilter); with ``gu`` fp32 [B,4] gate uniforms and the ADA ``state``, band i is on
+    for image b iff gu[b,i] < p.  An image with every band off gets the exact identity row (1, 0, ..., 0)."""
+    return _ada_matrix("filter", u, bits, gu, state)
+
+
+def _ada_filter(x, mat, adjoint):
+    x, mat, y = _ada_table_pass("ada_filter", 22, x, mat)
+    B, H, W, _ = x.shape
+    L = N.lib()
+    nb = L.sgx_ada_filter_workspace_bytes(B, H, W)
+    ws = N.workspace(nb, x.device)
+    N.check(L.sgx_ada_filter(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), N.ptr(ws), nb, N.stream()), "sgx_ada_filter")
+    return y
+
+
+AdaFilterFn, AdaFilterAdjFn = _adjoint_chain("AdaFilter", lambda x, adjoint, with_bias, mat: _ada_filter(x, mat, adjoint), 1, lin=False)
