@@ -391,7 +391,7 @@ int sgx_ada_color_matrix(const float* u, int u_stride, const float* gu, int gu_s
                          void* stream);
 int sgx_ada_color(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, int with_bias, void* stream);
 /* Image-space filtering, the fourth augmentation group of the ADA paper: policy bit 8192 = imgfilter, applied AFTER the colour ops
- * above (last in the canonical order) to fp32 [B][H][W][3] images; pixels that the earlier stages zeroed are filtered like any others.
+ * above (after them in the canonical order) to fp32 [B][H][W][3] images; pixels that the earlier stages zeroed are filtered like any others.
  * The filter bank is constant, 4 bands x 43 taps, built once in fp64 on the host:
  *   lo = [(1 - sqrt 3), (3 - sqrt 3), (3 + sqrt 3), (1 + sqrt 3)] / (4 sqrt 2)  (the sym2 low-pass),  hi[k] = lo[k] (-1)^k,
  *   lo2 = (lo * reverse(lo)) / 2,  hi2 = (hi * reverse(hi)) / 2  (7 taps each);  fb starts as the 4 x 1 column (1,0,0,0)^T; for i = 1, 2, 3:
@@ -440,6 +440,53 @@ size_t sgx_ada_filter_workspace_bytes(int B, int H, int W);
 int sgx_ada_filter(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* ws, size_t ws_bytes, void* stream);
 #define SGX_ADA_FILTER_PLAN_INTS 13
 int sgx_ada_filter_plan(int B, int H, int W, int adjoint, int aligned, int* out);
+/* Image-space corruptions, the last augmentation group of the ADA paper: policy_bits a subset of 16384 = noise, 32768 = imgcutout,
+ * applied in that order AFTER the filter above (last in the canonical order) to fp32 [B][H][W][3] images, as ONE pointwise pass
+ *   y = M (x + sigma n),   n a standard normal field, M the diagonal 0/1 mask of one rectangle per image
+ * (DiffAugment's own cutout, bit 4, is a different op: square, integer centre, applied before the geometric and colour stages; this
+ * one leaves true zeros at D's input).  u: DEVICE fp32, row b at u + b * u_stride (u_stride >= 6), six uniforms in [0,1); an op is on
+ * for an image when its bit is in policy_bits and either gu == NULL or its gate uniform is strictly below p = state[0] read on the
+ * device: gu row b at gu + b * gu_stride (gu_stride >= 2), column 0 gating noise, column 1 the cutout, each on its own; gu and state
+ * are both given or both NULL.
+ * sgx_ada_corrupt_table: one launch writes tab[b] = (sigma, k0, k1, x0, x1, y0, y1, 0) of every image, fp32 [B][8].  With
+ *   z(ua, ub) = clamp(sqrt(-2 ln(1 - ua)) cos(2 pi ub), -3, 3), the variate of the groups above:
+ *   noise on:   sigma = 0.1f * fabsf(z(u0, u1))  (the paper's noise_std = 0.1 half-normal, with the clamp of z);
+ *               k0 = min((uint32)(u2 * 16777216.0f), 16777215), k1 the same from u3: the field's key, stored as floats (exact: < 2^24)
+ *   noise off:  sigma = k0 = k1 = +0
+ *   cutout on:  with cx = u4 (columns), cy = u5 (rows), every product, sum and difference rounded to fp32 on its own:
+ *               a = cx * W,  q = 0.25f * W,  x0 = max(0, (int)floorf((a - q) - 0.5f) + 1),  x1 = min(W, (int)ceilf((a + q) - 0.5f)),
+ *               y0, y1 the same from cy and H; stored as floats.  The cut pixels are rows y0 <= i < y1 by columns x0 <= j < x1 (none
+ *               when x0 >= x1 or y0 >= y1): the paper's mask |(j + 0.5) / W - cx| < cutout_size / 2 with cutout_size = 0.5, up to fp32
+ *               rounding at the rectangle's edge
+ *   cutout off: x0 = x1 = y0 = y1 = +0
+ *   An image with both ops off (and every image when policy_bits is 0) gets the all-zero row exactly.  H, W >= 1.  Made once per D
+ *   evaluation; the forward, the linear part and the R1 double backward read the table, never p.
+ * sgx_ada_corrupt: x != y, any H, W >= 1 (3 H W >= 2^31: SGX_EUNSUPPORTED), B in 1..65535, one launch, no workspace, no atomics, nothing
+ *   written outside y.
+ *   mode 0, the forward:  a cut pixel is +0 in all three channels; elsewhere y = x + sigma * n when sigma != 0 (the product rounded to
+ *           fp32, then the sum: no contraction) and the bits of x when sigma == 0
+ *   mode 1, the linear part, which is its own adjoint (A = A^T = M):  a cut pixel is +0, elsewhere the bits of x (-0, infinities and
+ *           NaN payloads included)
+ *   An image whose rectangle is empty and whose sigma == 0 is copied bit for bit in both modes.  The noise of image b: for the flat
+ *   element e = (i W + j) 3 + c let q = e >> 2, r = e & 3 and
+ *     (o0, o1, o2, o3) = Philox4x32-10(counter (q, 0, 0, 0), key (k0, k1))      multipliers 0xD2511F53, 0xCD9E8D57; key increments
+ *                                                                               0x9E3779B9, 0xBB67AE85
+ *     for m = 0, 1:  ua = (o_2m >> 8) 2^-24,  ub = (o_2m+1 >> 8) 2^-24,  rad = sqrtf(-2 logf(1 - ua)),  (s, c) = sincospif(2 ub),
+ *                    n_2m = rad c,  n_2m+1 = rad s
+ *   element e takes n_r: no clamp, |n| <= sqrt(48 ln 2) ~ 5.77.  Nothing of the field is stored; two calls under one table give the
+ *   same bits.  With H W % 4 == 0 and 16-byte aligned bases a lane owns four consecutive pixels of the image's flat pixel order (three
+ *   16-byte loads and stores, the counters 3 g .. 3 g + 2 of its group g), else one pixel; both take a normal from the same function
+ *   and agree bit for bit.  No Philox round and no transcendental runs for an image or a mode that needs none.
+ * sgx_ada_corrupt_plan: host-only, what sgx_ada_corrupt will launch (the entry executes the same plan).  aligned: x and y are 16-byte
+ *   aligned.  out[SGX_ADA_CORRUPT_PLAN_INTS]: the number of launches (1), the kernel (0 ada_corrupt_px_kernel<MODE>,
+ *   1 ada_corrupt_vec_kernel<MODE>), MODE, grid x, grid y (= B); the block is 256 threads, no dynamic LDS.  Returns 0, or what the entry
+ *   returns for these arguments (SGX_EINVAL: B outside 1..65535, H or W < 1, a mode outside 0, 1, a NULL out; SGX_EUNSUPPORTED:
+ *   3 H W >= 2^31); out is zeroed on every error but a NULL out. */
+int sgx_ada_corrupt_table(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, int H, int W,
+                          float* tab, int B, void* stream);
+int sgx_ada_corrupt(const float* x, float* y, const float* tab, int B, int H, int W, int mode, void* stream);
+#define SGX_ADA_CORRUPT_PLAN_INTS 5
+int sgx_ada_corrupt_plan(int B, int H, int W, int mode, int aligned, int* out);
 /* Host-only query: what the image pass `entry` (SGX_AUG_PLAN_DIFFAUG / _GATED / _BLIT / _GEOM / _COLOR for sgx_diffaug / sgx_diffaug_gated /
  * sgx_diffaug_blit / sgx_ada_geom / sgx_ada_color) will launch for B images of H x W.  The entry points execute the same plan.  aligned:
  * both image bases are 16-byte aligned.  policy_bits is read for the first three entries only, with_bias for the colour pass only.

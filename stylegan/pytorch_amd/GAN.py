@@ -356,8 +356,9 @@ class Discriminator(nn.Module):
                  ada_kimg=500.0, ada_p_init=0.0, **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
-        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation,imgfilter' ('' = off); parsed here
-        # so that a bad policy fails at construction
+        # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation,imgfilter,noise,imgcutout'
+        # ('' = off; functional.ada_preset gives the strings of the ADA paper's categories); parsed here so that a bad policy fails at
+        # construction
         self.diffaug_policy = diffaug_policy or ""
         self._diffaug_bits = F.diffaug_policy_bits(self.diffaug_policy)
         if self._diffaug_bits and num_channels != 3:
@@ -449,9 +450,13 @@ class Discriminator(nn.Module):
     filter_override = None
     filter_gate_override = None
 
+    # and for the image-space corruptions (noise, imgcutout): their [B,6] draws and, under ADA, their [B,2] gate uniforms
+    corrupt_override = None
+    corrupt_gate_override = None
+
     def _diffaug(self, img):
         """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage,
-        then the colour stage, then the image-space filter."""
+        then the colour stage, then the image-space filter, then the image-space corruptions."""
         if self._diffaug_bits & F.DIFFAUG_PIXEL_MASK:
             img = self._diffaug_pixel(img, self._diffaug_bits & F.DIFFAUG_PIXEL_MASK)
         if self._diffaug_bits & F.DIFFAUG_GEOM_MASK:
@@ -460,6 +465,8 @@ class Discriminator(nn.Module):
             img = self._diffaug_color(img)
         if self._diffaug_bits & F.DIFFAUG_FILTER_MASK:
             img = self._diffaug_filter(img)
+        if self._diffaug_bits & F.DIFFAUG_CORRUPT_MASK:
+            img = self._diffaug_corrupt(img)
         return img
 
     def _stage_draws(self, img, nu, ng, u, gu, names=None):
@@ -491,6 +498,12 @@ class Discriminator(nn.Module):
         """imgfilter: [B,8] draws; [B,12] under ADA, columns 8..11 the gates of the four bands."""
         u, gu = self._stage_draws(img, 8, 4, self.filter_override, self.filter_gate_override, ("filter_override", "filter_gate_override"))
         return F.call(F.AdaFilterFn, img, F.ada_filter_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
+
+    def _diffaug_corrupt(self, img):
+        """noise, imgcutout: [B,6] draws; [B,8] under ADA, columns 6 and 7 the gates."""
+        u, gu = self._stage_draws(img, 6, 2, self.corrupt_override, self.corrupt_gate_override, ("corrupt_override", "corrupt_gate_override"))
+        tab = F.ada_corrupt_table(u, self._diffaug_bits, img.shape[1], img.shape[2], gu, self.ada_state if self.ada else None)
+        return F.call(F.AdaCorruptFn, img, tab)
 
     def _diffaug_geom(self, img):
         """scale, rotate, aniso: [B,5] draws; [B,8] under ADA, columns 5..7 the gates."""
@@ -1026,7 +1039,9 @@ class StyleGAN:
                None if self.dis.color_override is None else self.dis.color_override.data_ptr(),
                None if not self._ada_on() or self.dis.color_gate_override is None else self.dis.color_gate_override.data_ptr(),
                None if self.dis.filter_override is None else self.dis.filter_override.data_ptr(),
-               None if not self._ada_on() or self.dis.filter_gate_override is None else self.dis.filter_gate_override.data_ptr())
+               None if not self._ada_on() or self.dis.filter_gate_override is None else self.dis.filter_gate_override.data_ptr(),
+               None if self.dis.corrupt_override is None else self.dis.corrupt_override.data_ptr(),
+               None if not self._ada_on() or self.dis.corrupt_gate_override is None else self.dis.corrupt_gate_override.data_ptr())
         g = self._step_graphs.get(key)
         if g is None:
             g = self._step_graphs[key] = _StepGraph(self, kind, depth)

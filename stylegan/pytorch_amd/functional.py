@@ -2446,18 +2446,23 @@ DIFFAUG_COLOR_MASK = 256 | 512 | 1024 | 2048 | 4096
 DIFFAUG_FILTER_OPS = ("imgfilter",)
 DIFFAUG_FILTER_BITS = {"imgfilter": 8192}
 DIFFAUG_FILTER_MASK = 8192
+# the image-space corruptions of the ADA paper, applied last by their own kernel (``sgx_ada_corrupt``, further down).  ``imgcutout`` is the
+# paper's cutout (a rectangle of half the image's sides, true zeros at D's input); ``cutout`` above stays DiffAugment's
+DIFFAUG_CORRUPT_OPS = ("noise", "imgcutout")
+DIFFAUG_CORRUPT_BITS = {"noise": 16384, "imgcutout": 32768}
+DIFFAUG_CORRUPT_MASK = 16384 | 32768
 
 
 def diffaug_policy_bits(policy):
     """DiffAugment policy string -> policy bits.  A comma-separated subset of ``color,xflip,rot90,translation,cutout,scale,rotate,aniso,
-    brightness,contrast,lumaflip,hue,saturation,imgfilter`` in that (canonical) order, each at most once; '' or None: no augmentation.  Anything
-    else raises ValueError."""
+    brightness,contrast,lumaflip,hue,saturation,imgfilter,noise,imgcutout`` in that (canonical) order, each at most once; '' or None: no
+    augmentation.  Anything else raises ValueError."""
     if policy is None:
         return 0
     if not isinstance(policy, str):
         raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
-    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS + DIFFAUG_FILTER_OPS
-    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS, **DIFFAUG_FILTER_BITS}
+    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS + DIFFAUG_FILTER_OPS + DIFFAUG_CORRUPT_OPS
+    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS, **DIFFAUG_FILTER_BITS, **DIFFAUG_CORRUPT_BITS}
     bits, last = 0, -1
     for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
         if name not in order:
@@ -2468,6 +2473,22 @@ def diffaug_policy_bits(policy):
         bits |= known[name]
         last = k
     return bits
+
+
+def ada_preset(name):
+    """The policy STRING of one of the ADA paper's category names -- ``blit``, ``geom``, ``color``, ``filter``, ``noise``, ``cutout`` --
+    or of its pipelines ``bg``, ``bgc``, ``bgcf``, ``bgcfn``, ``bgcfnc``, for ``diffaug_policy``.  (The parser does not know these
+    names: ``diffaug_policy="bgc"`` is refused.  ``cutout`` here is the paper's, ``imgcutout``; DiffAugment's ``color`` and ``cutout``
+    are in no preset.)"""
+    groups = {"blit": ("xflip", "rot90", "translation"), "geom": DIFFAUG_GEOM_OPS, "color": DIFFAUG_COLOR_OPS, "filter": DIFFAUG_FILTER_OPS,
+              "noise": ("noise",), "cutout": ("imgcutout",)}
+    letters = {"b": "blit", "g": "geom", "c": "color", "f": "filter", "n": "noise"}
+    if name in groups:
+        return ",".join(groups[name])
+    if name in ("bg", "bgc", "bgcf", "bgcfn", "bgcfnc"):
+        ops = sum((groups[letters[ch]] for ch in name[:5]), ()) + (groups["cutout"] if len(name) == 6 else ())
+        return ",".join(ops)
+    raise ValueError(f"unknown ADA preset {name!r} (known: {','.join(groups)},bg,bgc,bgcf,bgcfn,bgcfnc)")
 
 
 def _rgb_images(x, who):
@@ -2695,3 +2716,68 @@ def _ada_filter(x, mat, adjoint):
 
 
 AdaFilterFn, AdaFilterAdjFn = _adjoint_chain("AdaFilter", lambda x, adjoint, with_bias, mat: _ada_filter(x, mat, adjoint), 1, lin=False)
+
+
+# The image-space corruptions of the ADA paper (noise, imgcutout; ``sgx_ada_corrupt_table`` / ``sgx_ada_corrupt``, include/sgx.h): one
+# streaming pass y = M (x + sigma n) under the table, the field n generated in the kernel and never stored.  The noise carries no
+# gradient and M is diagonal, so the linear part M g is its own adjoint: AdaCorruptFn's backward is AdaCorruptLinFn, whose backward is
+# itself -- the R1 double backward runs forward, linear, linear under one table, and the noise is generated once per D evaluation.
+def ada_corrupt_table(u, bits, H, W, gu=None, state=None):
+    """u fp32 [B,6] draws (rows of a wider draw are read in place) -> the fp32 [B,8] table (sigma, k0, k1, x0, x1, y0, y1, 0) of the
+    corruptions in ``bits`` (16384 noise, 32768 imgcutout) for images of H x W; with ``gu`` fp32 [B,2] gate uniforms and the ADA
+    ``state``, an op is on for image b iff gu[b,k] < p.  An image with both ops off gets the all-zero row exactly."""
+    who = "ada_corrupt_table"                                # (the checks of _ada_matrix; this entry also takes the image size)
+    if u.dim() != 2 or u.shape[1] != 6 or u.dtype != torch.float32:
+        raise N.SgxError(f"{who}: need fp32 [B,6] draws, got {tuple(u.shape)} {u.dtype}")
+    if (gu is None) != (state is None):
+        raise N.SgxError(f"{who}: gate uniforms and the ADA state come together or not at all")
+    u, B = _rows(u, 6), u.shape[0]
+    gp, gs = None, 0
+    if gu is not None:
+        if tuple(gu.shape) != (B, 2) or gu.dtype != torch.float32 or gu.device != u.device:
+            raise N.SgxError(f"{who}: need fp32 [{B},2] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
+        gu = _rows(gu, 2)
+        _ada_state_ok(state, u.device, who)
+        gp, gs = gu.data_ptr(), gu.stride(0)
+    _need_gpu(u)
+    tab = torch.empty(B, 8, dtype=torch.float32, device=u.device)
+    N.check(N.lib().sgx_ada_corrupt_table(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_CORRUPT_MASK, int(H), int(W),
+                                          N.ptr(tab), B, N.stream()), "sgx_ada_corrupt_table")
+    return tab
+
+
+def _ada_corrupt(x, tab, mode):
+    x, tab, y = _ada_table_pass("ada_corrupt", 8, x, tab)
+    if mode not in (0, 1):
+        raise N.SgxError(f"ada_corrupt: mode {mode!r} (0 forward, 1 linear part)")
+    B, H, W, _ = x.shape
+    N.check(N.lib().sgx_ada_corrupt(N.ptr(x), N.ptr(y), N.ptr(tab), B, H, W, int(mode), N.stream()), "sgx_ada_corrupt")
+    return y
+
+
+class AdaCorruptLinFn(Function):
+    """M g under the table: the linear part of AdaCorruptFn, its own adjoint and so its own backward."""
+
+    @staticmethod
+    def forward(ctx, g, tab):
+        ctx.save_for_backward(tab)
+        return _ada_corrupt(g, tab, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _bcall(AdaCorruptLinFn, g, *ctx.saved_tensors), None
+
+
+class AdaCorruptFn(Function):
+    """M (x + sigma n) under the table; backward = AdaCorruptLinFn, none when x needs no gradient (the D step's fakes)."""
+
+    @staticmethod
+    def forward(ctx, x, tab):
+        ctx.save_for_backward(tab)
+        return _ada_corrupt(x, tab, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return _bcall(AdaCorruptLinFn, g, *ctx.saved_tensors), None

@@ -98,6 +98,9 @@ SIGNATURES = {
     "sgx_ada_filter_workspace_bytes": (Z, [I, I, I]),
     "sgx_ada_filter": (I, [P, P, P, I, I, I, I, P, Z, P]),
     "sgx_ada_filter_plan": (I, [I, I, I, I, I, P]),
+    "sgx_ada_corrupt_table": (I, [P, I, P, I, P, I, I, I, P, I, P]),
+    "sgx_ada_corrupt": (I, [P, P, P, I, I, I, I, P]),
+    "sgx_ada_corrupt_plan": (I, [I, I, I, I, I, P]),
     "sgx_aug_plan": (I, [I, I, I, I, I, I, I, I, P]),
     "sgx_rgb_out_fade": (I, [P, P, I, I, F, P, P, F, F, P, P, I, I, I, I, I, P]),
     "sgx_rgb_wgrad_ws_bytes": (Z, [Z, I]),
