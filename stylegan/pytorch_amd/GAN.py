@@ -455,18 +455,14 @@ class Discriminator(nn.Module):
     corrupt_gate_override = None
 
     def _diffaug(self, img):
-        """The ops of the first five (on the DiffAugment / blitting kernels, called with their bits alone), then the geometric stage,
-        then the colour stage, then the image-space filter, then the image-space corruptions."""
-        if self._diffaug_bits & F.DIFFAUG_PIXEL_MASK:
-            img = self._diffaug_pixel(img, self._diffaug_bits & F.DIFFAUG_PIXEL_MASK)
-        if self._diffaug_bits & F.DIFFAUG_GEOM_MASK:
-            img = self._diffaug_geom(img)
-        if self._diffaug_bits & F.DIFFAUG_COLOR_MASK:
-            img = self._diffaug_color(img)
-        if self._diffaug_bits & F.DIFFAUG_FILTER_MASK:
-            img = self._diffaug_filter(img)
-        if self._diffaug_bits & F.DIFFAUG_CORRUPT_MASK:
-            img = self._diffaug_corrupt(img)
+        """The stages of ``functional.AUG_STAGES`` that the policy has ops of, in the table's order: the pixel stage (on the DiffAugment
+        / blitting kernels, called with its bits alone), then the table stages."""
+        pixel, *stages = F.AUG_STAGES
+        if self._diffaug_bits & pixel.mask:
+            img = self._diffaug_pixel(img, self._diffaug_bits & pixel.mask)
+        for stage in stages:
+            if self._diffaug_bits & stage.mask:
+                img = self._diffaug_stage(img, stage)
         return img
 
     def _stage_draws(self, img, nu, ng, u, gu, names=None):
@@ -489,26 +485,11 @@ class Discriminator(nn.Module):
 
     # The gates are turned into per-image bits (the first five ops) or folded into the per-image table (geometric, colour) ONCE per D
     # evaluation, here; the adjoint, the linear part and the R1 double backward of this evaluation read the bits or the table, never p.
-    def _diffaug_color(self, img):
-        """brightness, contrast, lumaflip, hue, saturation: [B,8] draws; [B,13] under ADA, columns 8..12 the gates."""
-        u, gu = self._stage_draws(img, 8, 5, self.color_override, self.color_gate_override, ("color_override", "color_gate_override"))
-        return F.call(F.AdaColorFn, img, F.ada_color_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
-
-    def _diffaug_filter(self, img):
-        """imgfilter: [B,8] draws; [B,12] under ADA, columns 8..11 the gates of the four bands."""
-        u, gu = self._stage_draws(img, 8, 4, self.filter_override, self.filter_gate_override, ("filter_override", "filter_gate_override"))
-        return F.call(F.AdaFilterFn, img, F.ada_filter_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
-
-    def _diffaug_corrupt(self, img):
-        """noise, imgcutout: [B,6] draws; [B,8] under ADA, columns 6 and 7 the gates."""
-        u, gu = self._stage_draws(img, 6, 2, self.corrupt_override, self.corrupt_gate_override, ("corrupt_override", "corrupt_gate_override"))
-        tab = F.ada_corrupt_table(u, self._diffaug_bits, img.shape[1], img.shape[2], gu, self.ada_state if self.ada else None)
-        return F.call(F.AdaCorruptFn, img, tab)
-
-    def _diffaug_geom(self, img):
-        """scale, rotate, aniso: [B,5] draws; [B,8] under ADA, columns 5..7 the gates."""
-        u, gu = self._stage_draws(img, 5, 3, self.geom_override, self.geom_gate_override, ("geom_override", "geom_gate_override"))
-        return F.call(F.AdaGeomFn, img, F.ada_geom_matrix(u, self._diffaug_bits, gu, self.ada_state if self.ada else None))
+    def _diffaug_stage(self, img, stage):
+        """One table stage: [B,nu] draws; [B,nu+ng] under ADA, columns nu.. the gates."""
+        u, gu = self._stage_draws(img, stage.nu, stage.ng, getattr(self, stage.hooks[0]), getattr(self, stage.hooks[1]), stage.hooks)
+        tab = F._ada_matrix(stage, u, self._diffaug_bits, gu, self.ada_state if self.ada else None, img.shape[1:3])
+        return F.call(getattr(F, stage.fn), img, tab)
 
     def _diffaug_pixel(self, img, bits):
         """color, translation, cutout: [B,7] draws; [B,10] under ADA, columns 7..9 the gates.  (No width check here: a wrong override

@@ -15,6 +15,7 @@ import contextlib
 import functools
 import os
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -2430,27 +2431,40 @@ def nchw_view(x_nhwc):
 # image (colour, translation, cutout for the seven draws u[b]).  The chain DiffAugFn -> DiffAugAdjFn -> DiffAugLinFn -> DiffAugAdjFn
 # closes under differentiation, so the R1 penalty's double backward runs through it.  With ``xflip`` or ``rot90`` in the policy (pixel
 # blitting, Karras et al., NeurIPS 2020) the draws are nine per image and the same chain runs on ``sgx_diffaug_blit``.
-DIFFAUG_OPS = ("color", "xflip", "rot90", "translation", "cutout")          # the canonical order: the order the ops are applied in
-DIFFAUG_BITS = {"color": 1, "translation": 2, "cutout": 4, "xflip": 8, "rot90": 16}    # the kernels' policy bits (not the op's index)
+#
+# The augmentation stages of the discriminator's input, in application order.  The parser, the presets, the table builder, the pass
+# wrappers and Discriminator._diffaug all read this table and restate nothing.  ``hooks`` names the two
+# Discriminator attributes that override the stage's draws and its ADA gate uniforms; ``bits`` maps the stage's ops, in canonical order
+# (the order they are applied in), to the kernels' policy bits (include/sgx.h; not the op's index) and ``mask`` is their union.  The
+# pixel stage (DiffAugment and blitting) has a call path of its own, further down.  Each of the four stages after it is one per-image
+# table per D evaluation and one pass under it: per image ``nu`` draws, ``ng`` gate uniforms and ``row`` floats of the table, built by
+# the library's ``entry`` (which also takes H, W where ``sized``) and applied by the Function named ``fn``.  ``imgcutout`` is the ADA
+# paper's cutout (a rectangle of half the image's sides, true zeros at D's input); ``cutout`` stays DiffAugment's.
+AugStage = namedtuple("AugStage", "name hooks bits mask nu ng row entry sized fn", defaults=(None,) * 6)
+
+
+def _stage(name, hooks, bits, *table):
+    return AugStage(name, hooks, bits, sum(bits.values()), *table)
+
+
+AUG_STAGES = (
+    _stage("pixel", ("diffaug_override", "ada_gate_override"), {"color": 1, "xflip": 8, "rot90": 16, "translation": 2, "cutout": 4}),
+    _stage("geom", ("geom_override", "geom_gate_override"), {"scale": 32, "rotate": 64, "aniso": 128},
+           5, 3, 8, "sgx_ada_geom_matrix", False, "AdaGeomFn"),
+    _stage("color", ("color_override", "color_gate_override"),
+           {"brightness": 256, "contrast": 512, "lumaflip": 1024, "hue": 2048, "saturation": 4096},
+           8, 5, 12, "sgx_ada_color_matrix", False, "AdaColorFn"),
+    _stage("filter", ("filter_override", "filter_gate_override"), {"imgfilter": 8192},
+           8, 4, 22, "sgx_ada_filter_matrix", False, "AdaFilterFn"),
+    _stage("corrupt", ("corrupt_override", "corrupt_gate_override"), {"noise": 16384, "imgcutout": 32768},
+           6, 2, 8, "sgx_ada_corrupt_table", True, "AdaCorruptFn"),
+)
+_STAGE = {s.name: s for s in AUG_STAGES}
+# the same facts under the names they had before the table
+((DIFFAUG_OPS, DIFFAUG_BITS, DIFFAUG_PIXEL_MASK), (DIFFAUG_GEOM_OPS, DIFFAUG_GEOM_BITS, DIFFAUG_GEOM_MASK),
+ (DIFFAUG_COLOR_OPS, DIFFAUG_COLOR_BITS, DIFFAUG_COLOR_MASK), (DIFFAUG_FILTER_OPS, DIFFAUG_FILTER_BITS, DIFFAUG_FILTER_MASK),
+ (DIFFAUG_CORRUPT_OPS, DIFFAUG_CORRUPT_BITS, DIFFAUG_CORRUPT_MASK)) = ((tuple(s.bits), s.bits, s.mask) for s in AUG_STAGES)
 DIFFAUG_BLIT_BITS = DIFFAUG_BITS["xflip"] | DIFFAUG_BITS["rot90"]
-# the general geometric group of the ADA paper, applied after the five ops above by its own kernels (``sgx_ada_geom``, further down)
-DIFFAUG_GEOM_OPS = ("scale", "rotate", "aniso")
-DIFFAUG_GEOM_BITS = {"scale": 32, "rotate": 64, "aniso": 128}
-DIFFAUG_GEOM_MASK = 32 | 64 | 128
-DIFFAUG_PIXEL_MASK = 31                                                      # the bits the DiffAugment / blitting entry points take
-# the colour group of the ADA paper, applied last by its own kernels (``sgx_ada_color``, further down)
-DIFFAUG_COLOR_OPS = ("brightness", "contrast", "lumaflip", "hue", "saturation")
-DIFFAUG_COLOR_BITS = {"brightness": 256, "contrast": 512, "lumaflip": 1024, "hue": 2048, "saturation": 4096}
-DIFFAUG_COLOR_MASK = 256 | 512 | 1024 | 2048 | 4096
-# the image-space filtering group of the ADA paper, applied after the colour group by its own kernels (``sgx_ada_filter``, further down)
-DIFFAUG_FILTER_OPS = ("imgfilter",)
-DIFFAUG_FILTER_BITS = {"imgfilter": 8192}
-DIFFAUG_FILTER_MASK = 8192
-# the image-space corruptions of the ADA paper, applied last by their own kernel (``sgx_ada_corrupt``, further down).  ``imgcutout`` is the
-# paper's cutout (a rectangle of half the image's sides, true zeros at D's input); ``cutout`` above stays DiffAugment's
-DIFFAUG_CORRUPT_OPS = ("noise", "imgcutout")
-DIFFAUG_CORRUPT_BITS = {"noise": 16384, "imgcutout": 32768}
-DIFFAUG_CORRUPT_MASK = 16384 | 32768
 
 
 def diffaug_policy_bits(policy):
@@ -2461,8 +2475,8 @@ def diffaug_policy_bits(policy):
         return 0
     if not isinstance(policy, str):
         raise ValueError(f"diffaug_policy must be a string, got {type(policy).__name__}")
-    order = DIFFAUG_OPS + DIFFAUG_GEOM_OPS + DIFFAUG_COLOR_OPS + DIFFAUG_FILTER_OPS + DIFFAUG_CORRUPT_OPS
-    known = {**DIFFAUG_BITS, **DIFFAUG_GEOM_BITS, **DIFFAUG_COLOR_BITS, **DIFFAUG_FILTER_BITS, **DIFFAUG_CORRUPT_BITS}
+    known = {op: bit for s in AUG_STAGES for op, bit in s.bits.items()}
+    order = tuple(known)
     bits, last = 0, -1
     for name in (s.strip() for s in policy.split(",")) if policy.strip() else ():
         if name not in order:
@@ -2480,7 +2494,7 @@ def ada_preset(name):
     or of its pipelines ``bg``, ``bgc``, ``bgcf``, ``bgcfn``, ``bgcfnc``, for ``diffaug_policy``.  (The parser does not know these
     names: ``diffaug_policy="bgc"`` is refused.  ``cutout`` here is the paper's, ``imgcutout``; DiffAugment's ``color`` and ``cutout``
     are in no preset.)"""
-    groups = {"blit": ("xflip", "rot90", "translation"), "geom": DIFFAUG_GEOM_OPS, "color": DIFFAUG_COLOR_OPS, "filter": DIFFAUG_FILTER_OPS,
+    groups = {"blit": ("xflip", "rot90", "translation"), **{g: tuple(_STAGE[g].bits) for g in ("geom", "color", "filter")},
               "noise": ("noise",), "cutout": ("imgcutout",)}
     letters = {"b": "blit", "g": "geom", "c": "color", "f": "filter", "n": "noise"}
     if name in groups:
@@ -2621,15 +2635,11 @@ def ada_update(real_logits, state, target, adjust_per_image, interval):
     return state
 
 
-# The three op groups that are one per-image table per D evaluation and one pass under it: per image the draws, the gate uniforms and
-# the floats of a table row, the group's policy bits, the library's entry point.
-_ADA_MATRIX = {"geom": (5, 3, 8, DIFFAUG_GEOM_MASK, "sgx_ada_geom_matrix"), "color": (8, 5, 12, DIFFAUG_COLOR_MASK, "sgx_ada_color_matrix"),
-               "filter": (8, 4, 22, DIFFAUG_FILTER_MASK, "sgx_ada_filter_matrix")}
-
-
-def _ada_matrix(group, u, bits, gu, state):
-    nu, ng, nm, mask, entry = _ADA_MATRIX[group]
-    who = f"ada_{group}_matrix"
+# The four table stages of AUG_STAGES: the per-image table of one D evaluation, and the checks every pass under it shares.
+def _ada_matrix(stage, u, bits, gu, state, size=None):
+    """``size``: the images' (H, W), for a stage whose entry point takes them (``sized``)."""
+    nu, ng, entry = stage.nu, stage.ng, stage.entry
+    who = entry[len("sgx_"):]
     if u.dim() != 2 or u.shape[1] != nu or u.dtype != torch.float32:
         raise N.SgxError(f"{who}: need fp32 [B,{nu}] draws, got {tuple(u.shape)} {u.dtype}")
     u = _rows(u, nu)
@@ -2644,12 +2654,15 @@ def _ada_matrix(group, u, bits, gu, state):
         _ada_state_ok(state, u.device, who)
         gp, gs = gu.data_ptr(), gu.stride(0)
     _need_gpu(u)
-    mat = torch.empty(B, nm, dtype=torch.float32, device=u.device)
-    N.check(getattr(N.lib(), entry)(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & mask, N.ptr(mat), B, N.stream()), entry)
+    mat = torch.empty(B, stage.row, dtype=torch.float32, device=u.device)
+    hw = (int(size[0]), int(size[1])) if stage.sized else ()
+    N.check(getattr(N.lib(), entry)(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & stage.mask, *hw, N.ptr(mat), B, N.stream()),
+            entry)
     return mat
 
 
-def _ada_table_pass(who, width, x, mat):
+def _ada_table_pass(stage, x, mat):
+    who, width = f"ada_{stage}", _STAGE[stage].row
     x = _rgb_images(x, who)
     if tuple(mat.shape) != (x.shape[0], width) or mat.dtype != torch.float32 or mat.device != x.device:
         raise N.SgxError(f"{who}: need an fp32 [{x.shape[0]},{width}] table on {x.device}, got {tuple(mat.shape)} {mat.dtype} on {mat.device}")
@@ -2662,11 +2675,11 @@ def ada_geom_matrix(u, bits, gu=None, state=None):
     """u fp32 [B,5] draws (rows of a wider draw are read in place) -> the fp32 [B,8] table {T^-1, T} of the geometric ops in ``bits``
     (32 scale, 64 rotate, 128 aniso); with ``gu`` fp32 [B,3] gate uniforms and the ADA ``state``, an op is on for image b iff
     gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0,1, 1,0,0,1)."""
-    return _ada_matrix("geom", u, bits, gu, state)
+    return _ada_matrix(_STAGE["geom"], u, bits, gu, state)
 
 
 def _ada_geom(x, mat, adjoint):
-    x, mat, y = _ada_table_pass("ada_geom", 8, x, mat)
+    x, mat, y = _ada_table_pass("geom", x, mat)
     B, H, W, _ = x.shape
     N.check(N.lib().sgx_ada_geom(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), N.stream()), "sgx_ada_geom")
     return y
@@ -2681,11 +2694,11 @@ def ada_color_matrix(u, bits, gu=None, state=None):
     """u fp32 [B,8] draws (rows of a wider draw are read in place) -> the fp32 [B,12] table {M row major, t} of the colour ops in ``bits``
     (256 brightness, 512 contrast, 1024 lumaflip, 2048 hue, 4096 saturation); with ``gu`` fp32 [B,5] gate uniforms and the ADA ``state``,
     an op is on for image b iff gu[b,k] < p.  An image with every op off gets the exact identity row (1,0,0, 0,1,0, 0,0,1, 0,0,0)."""
-    return _ada_matrix("color", u, bits, gu, state)
+    return _ada_matrix(_STAGE["color"], u, bits, gu, state)
 
 
 def _ada_color(x, mat, adjoint, with_bias):
-    x, mat, y = _ada_table_pass("ada_color", 12, x, mat)
+    x, mat, y = _ada_table_pass("color", x, mat)
     B, H, W, _ = x.shape
     N.check(N.lib().sgx_ada_color(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), int(with_bias), N.stream()), "sgx_ada_color")
     return y
@@ -2702,11 +2715,11 @@ def ada_filter_matrix(u, bits, gu=None, state=None):
     """u fp32 [B,8] draws (rows of a wider draw are read in place) -> the fp32 [B,22] table of half-rows c (the filter is
     h[k] = c[|k - 21|]) when ``bits`` has 8192 (imgfilter); with ``gu`` fp32 [B,4] gate uniforms and the ADA ``state``, band i is on
     for image b iff gu[b,i] < p.  An image with every band off gets the exact identity row (1, 0, ..., 0)."""
-    return _ada_matrix("filter", u, bits, gu, state)
+    return _ada_matrix(_STAGE["filter"], u, bits, gu, state)
 
 
 def _ada_filter(x, mat, adjoint):
-    x, mat, y = _ada_table_pass("ada_filter", 22, x, mat)
+    x, mat, y = _ada_table_pass("filter", x, mat)
     B, H, W, _ = x.shape
     L = N.lib()
     nb = L.sgx_ada_filter_workspace_bytes(B, H, W)
@@ -2726,28 +2739,11 @@ def ada_corrupt_table(u, bits, H, W, gu=None, state=None):
     """u fp32 [B,6] draws (rows of a wider draw are read in place) -> the fp32 [B,8] table (sigma, k0, k1, x0, x1, y0, y1, 0) of the
     corruptions in ``bits`` (16384 noise, 32768 imgcutout) for images of H x W; with ``gu`` fp32 [B,2] gate uniforms and the ADA
     ``state``, an op is on for image b iff gu[b,k] < p.  An image with both ops off gets the all-zero row exactly."""
-    who = "ada_corrupt_table"                                # (the checks of _ada_matrix; this entry also takes the image size)
-    if u.dim() != 2 or u.shape[1] != 6 or u.dtype != torch.float32:
-        raise N.SgxError(f"{who}: need fp32 [B,6] draws, got {tuple(u.shape)} {u.dtype}")
-    if (gu is None) != (state is None):
-        raise N.SgxError(f"{who}: gate uniforms and the ADA state come together or not at all")
-    u, B = _rows(u, 6), u.shape[0]
-    gp, gs = None, 0
-    if gu is not None:
-        if tuple(gu.shape) != (B, 2) or gu.dtype != torch.float32 or gu.device != u.device:
-            raise N.SgxError(f"{who}: need fp32 [{B},2] gate uniforms on {u.device}, got {tuple(gu.shape)} {gu.dtype} on {gu.device}")
-        gu = _rows(gu, 2)
-        _ada_state_ok(state, u.device, who)
-        gp, gs = gu.data_ptr(), gu.stride(0)
-    _need_gpu(u)
-    tab = torch.empty(B, 8, dtype=torch.float32, device=u.device)
-    N.check(N.lib().sgx_ada_corrupt_table(u.data_ptr(), u.stride(0), gp, gs, N.ptr(state), int(bits) & DIFFAUG_CORRUPT_MASK, int(H), int(W),
-                                          N.ptr(tab), B, N.stream()), "sgx_ada_corrupt_table")
-    return tab
+    return _ada_matrix(_STAGE["corrupt"], u, bits, gu, state, (H, W))
 
 
 def _ada_corrupt(x, tab, mode):
-    x, tab, y = _ada_table_pass("ada_corrupt", 8, x, tab)
+    x, tab, y = _ada_table_pass("corrupt", x, tab)
     if mode not in (0, 1):
         raise N.SgxError(f"ada_corrupt: mode {mode!r} (0 forward, 1 linear part)")
     B, H, W, _ = x.shape

@@ -10,6 +10,7 @@ import torch
 
 import color_cases as CC
 import color_ref as K
+from aug_gpu_util import small_dis_cpu as small_dis
 
 f32 = np.float32
 OLD_OPS = ("color", "xflip", "rot90", "translation", "cutout", "scale", "rotate", "aniso")
@@ -54,11 +55,6 @@ def test_misordered_duplicated_or_unknown_names_are_refused(bad):
 
 
 # ---------------------------------------------------------------------------------------------------- constructor, override widths
-def small_dis(**kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=8, blur_filter=[1, 2, 1], fmap_base=64, fmap_max=16, **kw)
-
-
 def test_constructor_and_state_dict():
     plain = small_dis(diffaug_policy="color")
     dis = small_dis(diffaug_policy="color,rotate,brightness,hue")

@@ -12,7 +12,8 @@ import ada_ref as A
 import aug_ref as AR
 import diffaug_ref as R
 import golden_util as gu
-from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
+from aug_gpu_util import dev_state, dparams, make_sg, mid_dis, small_dis
+from gpu_util import DEV, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
 from oracle import stylegan_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,6 @@ OPT = dict(learning_rate=0.003, beta_1=0, beta_2=0.99, eps=1e-8)
 f32 = np.float32
 EDGE = f32(R.EDGE)
 BIG_KIMG = 1e9                                   # p does not move within a test: 4 images * 1e-12 is far below half an ulp of 0.5 and 1
-
-
-def dev_state(p):
-    return torch.from_numpy(A.new_state(p)).to(DEV)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. the gates
@@ -172,12 +169,6 @@ def test_controller_crosses_the_target():
 
 
 # ----------------------------------------------------------------------------------------------------------- 4. pinned equivalences
-def mid_dis(policy=POLICY, **kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=MID["resolution"], num_channels=3, use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"],
-                         fmap_max=MID["fmap_max"], structure="linear", diffaug_policy=policy, **kw).to(DEV)
-
-
 def load_ada(module, params):
     """gpu_util.load_into for a module that may have the ``ada_state`` buffer, which the oracle's parameters do not: it keeps its own."""
     if getattr(module, "ada", False):
@@ -188,11 +179,6 @@ def load_ada(module, params):
 def spread_gates(B):
     """[B,3] gate uniforms spread over (0, 1): at any p in steps of 0.2 from 0.1 some are below and some above."""
     return torch.tensor([[((3 * b + k) * 5 % 12 + 0.5) / 12 for k in range(3)] for b in range(B)], dtype=torch.float32)
-
-
-@pytest.fixture(scope="module")
-def dparams():
-    return mid_params(torch.float64)[1]
 
 
 def test_pinned_p_equivalences(dparams):
@@ -236,7 +222,7 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
     from stylegan.pytorch_amd import Losses
     B, res = 4, 4 * 2 ** depth
     dp = dparams
-    dis = load_ada(mid_dis(ada_target=0.6, ada_p_init=0.5, ada_kimg=BIG_KIMG), dp)
+    dis = load_ada(mid_dis(POLICY, ada_target=0.6, ada_p_init=0.5, ada_kimg=BIG_KIMG), dp)
     dis.train()
     u = torch.from_numpy(R.edge_draws(B, seed=depth))
     gates_ = spread_gates(B)
@@ -277,20 +263,9 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
 
 
 # ------------------------------------------------------------------------------------------------------ 6. graph replay, moving p
-def make_sg(use_graphs=False, data_parallel=None, **ada):
-    from stylegan.pytorch_amd.GAN import StyleGAN
-    return StyleGAN(structure="linear", resolution=128, num_channels=3, latent_size=512,
-                    g_args=dict(latent_size=512, mapping_layers=MID["mapping_layers"], blur_filter=[1, 2, 1], truncation_psi=0.7,
-                                truncation_cutoff=8, fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"]),
-                    d_args=dict(use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"],
-                                diffaug_policy=POLICY, **ada),
-                    g_opt_args=OPT, d_opt_args=OPT, loss="logistic", d_repeats=1, use_ema=True, ema_decay=0.999,
-                    device=torch.device(DEV), use_graphs=use_graphs, data_parallel=data_parallel)
-
-
 def train_run(use_graphs, iters=4, seed=5):
     # 1 / (0.02 * 1000) = 0.05 per image: one update (interval 1) at batch 4 moves p by 0.2
-    sg = make_sg(use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
+    sg = make_sg(POLICY, use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
     gp, dp = mid_params(torch.float64)
     load_into(sg.gen, gp); load_ada(sg.dis, dp); load_into(sg.gen_shadow, gp)
     sg.gen.train(); sg.dis.train()
@@ -322,11 +297,6 @@ def test_graph_replay_matches_eager_with_a_moving_p():
 
 
 # ----------------------------------------------------------------------------------------------------------------- 7. fresh draws
-def small_dis(**kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=8, blur_filter=[1, 2, 1], fmap_base=64, fmap_max=16, **kw).to(DEV)
-
-
 def test_fresh_gates_statistics(monkeypatch):
     from stylegan.pytorch_amd import functional as F
     B, p = 4096, 0.3
@@ -398,14 +368,14 @@ def test_yaml_ada_trains(tmp_path):
 def test_data_parallel_with_ada_is_refused():
     group = types.SimpleNamespace(world_size=2)                              # (all the constructor reads of it before it refuses)
     with pytest.raises(ValueError, match="not supported"):
-        make_sg(data_parallel=group, ada_target=0.6)
+        make_sg(POLICY, data_parallel=group, ada_target=0.6)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 11. default path
 def test_default_path_draws_as_before(dparams):
     """ada_target absent: a policy-on training forward is torch.rand(B, 7) and nothing else on the device generator."""
     B = 4
-    on = load_into(mid_dis(), dparams)
+    on = load_into(mid_dis(POLICY), dparams)
     plain = load_into(mid_dis(""), dparams)
     on.train(); plain.train()
     x = gu.seeded((B, 3, 128, 128), 29).to(DEV)

@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 import torch
 
-import ada_ref as A
 import aug_ref as AR
 import blit_cases as C
 import blit_ref as Bl
 import golden_util as gu
-from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
+from aug_gpu_util import dev_state, dparams, load_ada, make_sg, mid_dis, small_dis
+from gpu_util import DEV, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
 from oracle import stylegan_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +28,6 @@ BIG_KIMG = 1e9                                   # p does not move within a test
 GUARD = 64                                       # floats around y (a multiple of 4: y keeps its 16-byte alignment)
 SENTINEL = 12345.5
 MODES = ((False, True), (False, False), (True, False))                     # (adjoint, with_bias)
-
-
-def dev_state(p):
-    return torch.from_numpy(A.new_state(p)).to(DEV)
 
 
 def run_blit(xd, ud, bitsd, policy, adjoint, with_bias):
@@ -289,23 +285,6 @@ def test_first_and_second_order_through_the_functions():
 
 
 # ------------------------------------------------------------------------------------------------------------------- 7. network
-def mid_dis(policy=FULL, **kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=MID["resolution"], num_channels=3, use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"],
-                         fmap_max=MID["fmap_max"], structure="linear", diffaug_policy=policy, **kw).to(DEV)
-
-
-def load_ada(module, params):
-    if getattr(module, "ada", False):
-        params = dict(params, ada_state=module.ada_state.detach().clone())
-    return load_into(module, params)
-
-
-@pytest.fixture(scope="module")
-def dparams():
-    return mid_params(torch.float64)[1]
-
-
 def patch_oracle(monkeypatch, u, img_bits):
     """Every oracle D evaluation sees the per-image restatement with the draws ``u`` and the bits the gates must give."""
     orig = O.discriminator
@@ -322,7 +301,7 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
     from stylegan.pytorch_amd import Losses
     B, res = C.NET_B, 4 * 2 ** depth
     dp = dparams
-    dis = load_ada(mid_dis(ada_target=0.6, ada_p_init=C.NET_P, ada_kimg=BIG_KIMG), dp)
+    dis = load_ada(mid_dis(FULL, ada_target=0.6, ada_p_init=C.NET_P, ada_kimg=BIG_KIMG), dp)
     dis.train()
     u, gates_, bits = C.network_draws(depth)
     ks = [Bl.params9(u[b], res, res, bits[b])["k"] for b in range(B)]
@@ -363,20 +342,9 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
 
 
 # ------------------------------------------------------------------------------------------------------ 8. graph replay, moving p
-def make_sg(use_graphs=False, **ada):
-    from stylegan.pytorch_amd.GAN import StyleGAN
-    return StyleGAN(structure="linear", resolution=128, num_channels=3, latent_size=512,
-                    g_args=dict(latent_size=512, mapping_layers=MID["mapping_layers"], blur_filter=[1, 2, 1], truncation_psi=0.7,
-                                truncation_cutoff=8, fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"]),
-                    d_args=dict(use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"],
-                                diffaug_policy=FULL, **ada),
-                    g_opt_args=OPT, d_opt_args=OPT, loss="logistic", d_repeats=1, use_ema=True, ema_decay=0.999,
-                    device=torch.device(DEV), use_graphs=use_graphs)
-
-
 def train_run(use_graphs, iters=4, seed=5):
     # 1 / (0.02 * 1000) = 0.05 per image: one update (interval 1) at batch 4 moves p by 0.2
-    sg = make_sg(use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
+    sg = make_sg(FULL, use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
     gp, dp = mid_params(torch.float64)
     load_into(sg.gen, gp); load_ada(sg.dis, dp); load_into(sg.gen_shadow, gp)
     sg.gen.train(); sg.dis.train()
@@ -410,7 +378,7 @@ def test_graph_replay_matches_eager_with_a_moving_p():
 def test_training_forward_draws_nine_or_fourteen(dparams, ada):
     B = 4
     kw = dict(ada_target=0.6, ada_p_init=0.5, ada_kimg=BIG_KIMG) if ada else {}
-    on = load_ada(mid_dis(**kw), dparams)
+    on = load_ada(mid_dis(FULL, **kw), dparams)
     plain = load_into(mid_dis(""), dparams)
     on.train(); plain.train()
     x = gu.seeded((B, 3, 128, 128), 29).to(DEV)
@@ -432,11 +400,6 @@ def test_training_forward_draws_nine_or_fourteen(dparams, ada):
 
 
 # ------------------------------------------------------------------------------------------------------ 10. fresh-draw statistics
-def small_dis(**kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=8, blur_filter=[1, 2, 1], fmap_base=64, fmap_max=16, **kw).to(DEV)
-
-
 def test_fresh_orientations_are_uniform():
     B, N_ = 4096, 8
     dis = small_dis(diffaug_policy="xflip,rot90")

@@ -22,9 +22,10 @@ import geom_ref as G
 import golden_util as gu
 import streaming_ref as SR
 import test_gpu_filter as TF
+from aug_gpu_util import bits_equal, dev_state, small_dis
 from gpu_util import DEV, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
 from oracle import stylegan_oracle as O
-from test_gpu_filter import BIG_KIMG, FULL14, bits_equal, dev_state, on_device, recorded, small_dis
+from test_gpu_filter import BIG_KIMG, FULL14, recorded
 
 pytestmark = pytest.mark.gpu
 

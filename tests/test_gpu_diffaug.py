@@ -9,6 +9,7 @@ import torch
 import aug_ref as AR
 import diffaug_ref as R
 import golden_util as gu
+from aug_gpu_util import mid_dis
 from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
 from oracle import stylegan_oracle as O
 
@@ -69,19 +70,13 @@ def patch_oracle(monkeypatch, u, bits):
     monkeypatch.setattr(O, "discriminator", discriminator)
 
 
-def mid_dis(policy=POLICY):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=MID["resolution"], num_channels=3, use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"],
-                         fmap_max=MID["fmap_max"], structure="linear", diffaug_policy=policy).to(DEV)
-
-
 @pytest.mark.parametrize("depth,alpha", [(5, 0.5), (3, 0.3)])
 def test_network_first_and_second_order_vs_oracle(monkeypatch, depth, alpha):
     """D(x), the R1 value and every D parameter gradient of the logistic D loss (R1 included: second order through the augmentation)."""
     from stylegan.pytorch_amd import Losses
     B, res = 4, 4 * 2 ** depth
     gp, dp = mid_params(torch.float64)
-    dis = load_into(mid_dis(), dp)
+    dis = load_into(mid_dis(POLICY), dp)
     dis.train()
     u = torch.from_numpy(R.edge_draws(B, seed=depth))
     dis.diffaug_override = u.to(DEV)
@@ -207,7 +202,7 @@ def test_graph_replay_matches_eager_with_pinned_draws():
 
 def test_replayed_draws_are_fresh():
     """A captured D(x) draws new augmentation parameters at every replay (torch's graph-safe generator), nothing is baked in."""
-    dis = load_into(mid_dis(), mid_params(torch.float64)[1])
+    dis = load_into(mid_dis(POLICY), mid_params(torch.float64)[1])
     dis.train()
     x = gu.seeded((4, 3, 128, 128), 9).to(DEV)
     s = torch.cuda.Stream()
@@ -255,7 +250,7 @@ def test_empty_policy_is_the_default_path():
         outs.append(d(x, 5, 0.5).detach())
         states.append(torch.cuda.get_rng_state())
     assert torch.equal(outs[0], outs[1]) and torch.equal(states[0], states[1])
-    on = load_into(mid_dis(), dp)
+    on = load_into(mid_dis(POLICY), dp)
     on.train()
     torch.cuda.manual_seed(123)
     on(x, 5, 0.5)

@@ -13,7 +13,6 @@ import numpy as np
 import pytest
 import torch
 
-import ada_ref as A
 import aug_ref as AR
 import blit_ref as Bl
 import color_cases as CC
@@ -23,7 +22,8 @@ import geom_cases as GC
 import geom_ref as G
 import golden_util as gu
 import streaming_ref as SR
-from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
+from aug_gpu_util import bits_equal, dev_state, load_ada, make_sg, mid_dis, on_device, small_dis
+from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise  # noqa: F401  (MID: test_gpu_corrupt reads it here)
 from oracle import stylegan_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -43,17 +43,6 @@ MATRIX_ERR_MEASURED = 3.35e-7
 MATRIX_TOL = 4 * MATRIX_ERR_MEASURED
 assert MATRIX_TOL <= 1e-5
 MATRIX_B = 16
-
-
-def dev_state(p):
-    return torch.from_numpy(A.new_state(p)).to(DEV)
-
-
-def on_device(t, off=0):
-    buf = torch.zeros(t.numel() + off, device=DEV)
-    v = buf[off:].view(t.shape)
-    v.copy_(t.to(DEV))
-    return v
 
 
 def lib_plan(B, H, W, adjoint, aligned):
@@ -107,10 +96,6 @@ def run_filter(xd, matd, adjoint):
 
 def expected_note(H, W, off):
     return "ada_filter_tile" if W % 4 == 0 and off == 0 and H >= TILE_MIN and W >= TILE_MIN else "ada_filter_px"
-
-
-def bits_equal(a, b):
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
 
 
 def device_table(B, seed=0, identity=()):
@@ -260,11 +245,6 @@ def test_identity_rows_copy_special_values(off, H, W):
 
 
 # ------------------------------------------------------------------------------------------------------------- 6. continuity
-def small_dis(**kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=8, blur_filter=[1, 2, 1], fmap_base=64, fmap_max=16, **kw).to(DEV)
-
-
 def recorded(fn):
     from stylegan.pytorch_amd import native as N
     N.prof_start(1)
@@ -393,18 +373,6 @@ def test_first_and_second_order_through_the_functions():
 
 
 # ------------------------------------------------------------------------------------------------------------------- 9. network
-def mid_dis(policy=FULL14, **kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=MID["resolution"], num_channels=3, use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"],
-                         fmap_max=MID["fmap_max"], structure="linear", diffaug_policy=policy, **kw).to(DEV)
-
-
-def load_ada(module, params):
-    if getattr(module, "ada", False):
-        params = dict(params, ada_state=module.ada_state.detach().clone())
-    return load_into(module, params)
-
-
 def filter_network_draws(depth):
     """-> (u [4,8], gate uniforms [4,4], on [4,4]) at p = 0.5: image 0 every band off, image 3 every band on, 1 and 2 split them."""
     on_, off_ = 0.25, 0.75
@@ -421,7 +389,7 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch):
     depth, alpha = 3, 0.3
     B, res = CC.NET_B, 4 * 2 ** depth
     dp = mid_params(torch.float64)[1]
-    dis = load_ada(mid_dis(ada_target=0.6, ada_p_init=CC.NET_P, ada_kimg=BIG_KIMG), dp)
+    dis = load_ada(mid_dis(FULL14, ada_target=0.6, ada_p_init=CC.NET_P, ada_kimg=BIG_KIMG), dp)
     dis.train()
     u9, gates5, bits5 = GC.C.network_draws(depth)
     u5, gates3, bits3 = GC.network_draws(depth)
@@ -479,20 +447,9 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ 10. graph replay, moving p
-def make_sg(use_graphs=False, **ada):
-    from stylegan.pytorch_amd.GAN import StyleGAN
-    return StyleGAN(structure="linear", resolution=128, num_channels=3, latent_size=512,
-                    g_args=dict(latent_size=512, mapping_layers=MID["mapping_layers"], blur_filter=[1, 2, 1], truncation_psi=0.7,
-                                truncation_cutoff=8, fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"]),
-                    d_args=dict(use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"],
-                                diffaug_policy=FULL14, **ada),
-                    g_opt_args=OPT, d_opt_args=OPT, loss="logistic", d_repeats=1, use_ema=True, ema_decay=0.999,
-                    device=torch.device(DEV), use_graphs=use_graphs)
-
-
 def train_run(use_graphs, iters=4, seed=5):
     # 1 / (0.02 * 1000) = 0.05 per image: one update (interval 1) at batch 4 moves p by 0.2
-    sg = make_sg(use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
+    sg = make_sg(FULL14, use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
     gp, dp = mid_params(torch.float64)
     load_into(sg.gen, gp); load_ada(sg.dis, dp); load_into(sg.gen_shadow, gp)
     sg.gen.train(); sg.dis.train()

@@ -10,13 +10,13 @@ import numpy as np
 import pytest
 import torch
 
-import ada_ref as A
 import aug_ref as AR
 import blit_ref as Bl
 import geom_cases as GC
 import geom_ref as G
 import golden_util as gu
-from gpu_util import DEV, MID, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
+from aug_gpu_util import dev_state, dparams, load_ada, make_sg, mid_dis, nchw, nhwc, on_device, recorded, small_dis
+from gpu_util import DEV, MID_DEPTH, load_into, mid_noises, mid_params, pin_noise
 from oracle import stylegan_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -33,17 +33,6 @@ EPS = 2.0 ** -24
 MATRIX_ERR_MEASURED = 2.11e-7
 MATRIX_TOL = 4 * MATRIX_ERR_MEASURED
 assert MATRIX_TOL <= 1e-5
-
-
-def dev_state(p):
-    return torch.from_numpy(A.new_state(p)).to(DEV)
-
-
-def on_device(t, off=0):
-    buf = torch.zeros(t.numel() + off, device=DEV)
-    v = buf[off:].view(t.shape)
-    v.copy_(t.to(DEV))
-    return v
 
 
 def run_geom(xd, matd, adjoint):
@@ -71,14 +60,6 @@ def run_geom(xd, matd, adjoint):
 
 def expected_note(W, off):
     return "ada_geom_tile" if W % 4 == 0 and off == 0 else "ada_geom_px"
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1)
 
 
 def rot(deg):
@@ -290,23 +271,6 @@ def test_forward_column_is_adjoint_row_bit_for_bit():
 
 
 # ------------------------------------------------------------------------------------------------------------- 5. continuity
-def small_dis(**kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=8, blur_filter=[1, 2, 1], fmap_base=64, fmap_max=16, **kw).to(DEV)
-
-
-def recorded(fn):
-    from stylegan.pytorch_amd import native as N
-    N.prof_start(1)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        N.prof_start(0)
-    AR.assert_records_are_planned(N)                                        # every image-pass launch: a launch sgx_aug_plan reports for its call
-    return out, [r[4].split(" ")[0] for r in N.prof_records()]
-
-
 def test_old_policies_launch_what_they_launched():
     from stylegan.pytorch_amd import functional as F
     B = 8
@@ -409,23 +373,6 @@ def test_first_and_second_order_through_the_functions():
 
 
 # ------------------------------------------------------------------------------------------------------------------- 6. network
-def mid_dis(policy=GC.FULL8, **kw):
-    from stylegan.pytorch_amd.GAN import Discriminator
-    return Discriminator(resolution=MID["resolution"], num_channels=3, use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"],
-                         fmap_max=MID["fmap_max"], structure="linear", diffaug_policy=policy, **kw).to(DEV)
-
-
-def load_ada(module, params):
-    if getattr(module, "ada", False):
-        params = dict(params, ada_state=module.ada_state.detach().clone())
-    return load_into(module, params)
-
-
-@pytest.fixture(scope="module")
-def dparams():
-    return mid_params(torch.float64)[1]
-
-
 @pytest.mark.parametrize("depth,alpha", [(5, 0.5), (3, 0.3)])
 def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, alpha):
     """D(x), the R1 value and every D parameter gradient of the logistic D loss under the eight-op policy with per-image gates (p = 0.5
@@ -440,7 +387,7 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
     from stylegan.pytorch_amd import functional as F
     B, res = GC.NET_B, 4 * 2 ** depth
     dp = dparams
-    dis = load_ada(mid_dis(ada_target=0.6, ada_p_init=GC.NET_P, ada_kimg=BIG_KIMG), dp)
+    dis = load_ada(mid_dis(GC.FULL8, ada_target=0.6, ada_p_init=GC.NET_P, ada_kimg=BIG_KIMG), dp)
     dis.train()
     u9, gates5, bits5 = GC.C.network_draws(depth)
     u5, gates3, bits3 = GC.network_draws(depth)
@@ -493,20 +440,9 @@ def test_network_first_and_second_order_vs_oracle(monkeypatch, dparams, depth, a
 
 
 # ------------------------------------------------------------------------------------------------------ graph replay, moving p
-def make_sg(use_graphs=False, **ada):
-    from stylegan.pytorch_amd.GAN import StyleGAN
-    return StyleGAN(structure="linear", resolution=128, num_channels=3, latent_size=512,
-                    g_args=dict(latent_size=512, mapping_layers=MID["mapping_layers"], blur_filter=[1, 2, 1], truncation_psi=0.7,
-                                truncation_cutoff=8, fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"]),
-                    d_args=dict(use_wscale=True, blur_filter=[1, 2, 1], fmap_base=MID["fmap_base"], fmap_max=MID["fmap_max"],
-                                diffaug_policy=GC.FULL8, **ada),
-                    g_opt_args=OPT, d_opt_args=OPT, loss="logistic", d_repeats=1, use_ema=True, ema_decay=0.999,
-                    device=torch.device(DEV), use_graphs=use_graphs)
-
-
 def train_run(use_graphs, iters=4, seed=5):
     # 1 / (0.02 * 1000) = 0.05 per image: one update (interval 1) at batch 4 moves p by 0.2
-    sg = make_sg(use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
+    sg = make_sg(GC.FULL8, use_graphs, ada_target=0.6, ada_interval=1, ada_kimg=0.02, ada_p_init=0.5)
     gp, dp = mid_params(torch.float64)
     load_into(sg.gen, gp); load_ada(sg.dis, dp); load_into(sg.gen_shadow, gp)
     sg.gen.train(); sg.dis.train()
