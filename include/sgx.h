@@ -350,10 +350,34 @@ int sgx_ada_gates_n(const float* gu, int gu_stride, int n_ops, const float* stat
  *   acc += w * v, both roundings in fp32, taps in the order (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1), candidates row by row.
  *   x != y, any H, W >= 1, no workspace, gathers only, no atomics: bit-reproducible.  With W % 4 == 0 and 16-byte aligned bases
  *   a block resamples a 32 x 32 tile (and copies an identity image with 16-byte loads and stores).  Replaces the augment pipe's isotropic scale, arbitrary rotation and anisotropic scale (with bilinear
- *   taps and zero padding instead of its band-limited filters and reflection padding). */
+ *   taps instead of its band-limited filters; zero padding here, its reflection padding in sgx_ada_geom_reflect).
+ * sgx_ada_geom_reflect: the same resample under the same table (sgx_ada_geom_matrix is shared) with REFLECTION padding.  Per axis of
+ *   length N >= 2 a tap index t is valid iff -(N-1) <= t <= 2 (N-1) -- one reflection period, np.pad(mode="reflect") with pad N-1 --
+ *   and a valid tap reads the pixel r(t) = -t for t < 0, 2 (N-1) - t for t > N-1, t otherwise.  The weight is taken at the UNREFLECTED
+ *   t; a tap beyond one period contributes zero (the paper likewise clamps its margin to N-1 and samples zeros beyond it).
+ *   adjoint = 0:  y(p) = sum over the valid taps t = floor(s_p) + {0,1}^2 of w(s_p, t) x(r(t)), taps in sgx_ada_geom's order; a pixel
+ *                 with no valid tap is +0;
+ *   adjoint = 1:  y(q) = sum_p sum over the valid taps t of p with r(t) = q of w(s_p, t) x(p), as a gather with no atomics.  Per axis
+ *                 the pixel index q has up to three pre-images under r: q itself, -q when q >= 1, 2 (N-1) - q when q <= N-2 (distinct,
+ *                 all inside the period), so up to nine unreflected positions q' per pixel.  For each q' the candidate box of
+ *                 sgx_ada_geom's adjoint is walked with q' in place of q in both the box centre and the weight.  Summation order:
+ *                 the mirrors row-major -- the row's (q, -q, 2 (H-1) - q) outer, the column's inner -- and within a mirror the
+ *                 candidates row by row, into ONE fp32 accumulator that starts at +0.
+ *   s_p, w and acc += w * v are sgx_ada_geom's expressions, so the adjoint's coefficients are the forward's bit for bit, and an
+ *   image whose taps all stay inside the image gets sgx_ada_geom's bits in both directions.  An identity row is a bit-for-bit copy.
+ *   x != y; H, W >= 2 (SGX_EINVAL below that); the other rejections are sgx_ada_geom's.  No workspace, no atomics, nothing written
+ *   outside y.  With W % 4 == 0 and 16-byte aligned bases a block resamples a 32 x 32 tile, else a thread one pixel.
+ * sgx_ada_geom_reflect_plan: host-only, what sgx_ada_geom_reflect will launch (the entry executes the same plan).  aligned: x and y are
+ *   16-byte aligned.  out[SGX_ADA_GEOM_REFLECT_PLAN_INTS]: the number of launches (1), the kernel (0 ada_geom_reflect_px_kernel<ADJ>,
+ *   1 ada_geom_reflect_tile_kernel<ADJ>), ADJ, grid x, grid y (= B), tiles of 32 x 32 pixels per row of tiles (0 for the px kernel);
+ *   the block is 256 threads, no dynamic LDS.  Returns 0, or what the entry returns for these arguments (SGX_EINVAL: B outside
+ *   1..65535, H or W < 2, a NULL out; SGX_EUNSUPPORTED: 3 H W >= 2^31); out is zeroed on every error but a NULL out. */
 int sgx_ada_geom_matrix(const float* u, int u_stride, const float* gu, int gu_stride, const float* state, int policy_bits, float* mat, int B,
                         void* stream);
 int sgx_ada_geom(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream);
+int sgx_ada_geom_reflect(const float* x, float* y, const float* mat, int B, int H, int W, int adjoint, void* stream);
+#define SGX_ADA_GEOM_REFLECT_PLAN_INTS 6
+int sgx_ada_geom_reflect_plan(int B, int H, int W, int adjoint, int aligned, int* out);
 /* The colour transformations, the third augmentation group of the ADA paper: policy_bits a subset of 256 = brightness, 512 = contrast,
  * 1024 = lumaflip, 2048 = hue, 4096 = saturation, applied in that order AFTER the ops above, composed per image into one affine map of
  * the RGB vector of fp32 [B][H][W][3] images.  u: DEVICE fp32, row b at u + b * u_stride (u_stride >= 8), eight uniforms in [0,1); with

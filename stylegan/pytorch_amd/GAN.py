@@ -353,7 +353,7 @@ class Discriminator(nn.Module):
     def __init__(self, resolution, num_channels=3, conditional=False, n_classes=0, fmap_base=8192, fmap_decay=1.0,
                  fmap_max=512, nonlinearity='lrelu', use_wscale=True, mbstd_group_size=4, mbstd_num_features=1,
                  blur_filter=None, structure='linear', act_dtype=torch.float32, diffaug_policy="", ada_target=0.0, ada_interval=4,
-                 ada_kimg=500.0, ada_p_init=0.0, **kwargs):
+                 ada_kimg=500.0, ada_p_init=0.0, geom_padding="zeros", **kwargs):
         super().__init__()
         # DiffAugment (Zhao et al., NeurIPS 2020) of every image D sees while training: a canonical-order subset of
         # 'color,xflip,rot90,translation,cutout,scale,rotate,aniso,brightness,contrast,lumaflip,hue,saturation,imgfilter,noise,imgcutout'
@@ -364,6 +364,11 @@ class Discriminator(nn.Module):
         if self._diffaug_bits and num_channels != 3:
             raise ValueError(f"diffaug_policy {self.diffaug_policy!r} needs num_channels == 3, got {num_channels}: the DiffAugment / ADA "
                              "kernels are 3-channel by construction (the colour ops mix R, G and B)")
+        # what the geometric stage (scale, rotate, aniso) reads outside the image: "zeros", or the ADA paper's "reflect" (one
+        # reflection period, zeros beyond it); fixed for the model's lifetime, inert for a policy without a geometric op
+        if not isinstance(geom_padding, str) or geom_padding not in F.GEOM_PADDINGS:
+            raise ValueError(f"geom_padding must be one of {', '.join(map(repr, F.GEOM_PADDINGS))}, got {geom_padding!r}")
+        self.geom_padding = geom_padding
         # ADA (Karras et al., NeurIPS 2020) on top of the policy: each op with probability p, p steered on the device towards
         # E[sign(D(real))] == ada_target (0: off -- no buffer, the policy applies always, exactly the code path without these keys)
         self.ada_target, self.ada_interval = float(ada_target), int(ada_interval)
@@ -489,7 +494,8 @@ class Discriminator(nn.Module):
         """One table stage: [B,nu] draws; [B,nu+ng] under ADA, columns nu.. the gates."""
         u, gu = self._stage_draws(img, stage.nu, stage.ng, getattr(self, stage.hooks[0]), getattr(self, stage.hooks[1]), stage.hooks)
         tab = F._ada_matrix(stage, u, self._diffaug_bits, gu, self.ada_state if self.ada else None, img.shape[1:3])
-        return F.call(getattr(F, stage.fn), img, tab)
+        fn = F.GEOM_PADDINGS[self.geom_padding] if stage.name == "geom" else stage.fn
+        return F.call(getattr(F, fn), img, tab)
 
     def _diffaug_pixel(self, img, bits):
         """color, translation, cutout: [B,7] draws; [B,10] under ADA, columns 7..9 the gates.  (No width check here: a wrong override

@@ -134,7 +134,9 @@ def default_cfg():
                     # ADA (Karras et al., NeurIPS 2020): each op of the policy with probability p, p steered so that
                     # E[sign(D(real))] meets ada_target (0 = off, the paper uses 0.6); one controller update per ada_interval
                     # D steps; ada_kimg thousand images for p to travel from 0 to 1; p starts at ada_p_init
-                    "ada_target": 0.0, "ada_interval": 4, "ada_kimg": 500.0, "ada_p_init": 0.0},
+                    "ada_target": 0.0, "ada_interval": 4, "ada_kimg": 500.0, "ada_p_init": 0.0,
+                    # what scale, rotate, aniso read outside the image: "zeros", or the ADA paper's "reflect" (no black wedges)
+                    "geom_padding": "zeros"},
             "g_optim": {"learning_rate": 0.003, "beta_1": 0, "beta_2": 0.99, "eps": 1e-8},        # :79-83
             "d_optim": {"learning_rate": 0.003, "beta_1": 0, "beta_2": 0.99, "eps": 1e-8},        # :88-92
         },

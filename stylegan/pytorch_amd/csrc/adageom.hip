@@ -8,13 +8,9 @@
 // sgx_ada_geom_matrix turns one D evaluation's draws (and, under ADA, its gate uniforms against p) into the per-image table
 // {T^-1, T} once; the forward, the adjoint and the R1 double backward read the table, never p.  An image with its three ops off gets
 // the exact identity row, which IS its flag: both resample kernels copy such an image (a block-uniform branch).
-#include "aug.h"
+#include "adageom.h"
 
 enum { DG_SCALE = 32, DG_ROTATE = 64, DG_ANISO = 128, DG_OPS = DG_SCALE | DG_ROTATE | DG_ANISO };
-constexpr int DG_BLOCK = 256;
-constexpr float DG_MARGIN = 0.03125f;               // slack of the adjoint's candidate box, in pixels (covers T T^-1 != I in fp32)
-
-typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));   // one 12-byte pixel at a 4-byte aligned address (dwordx3)
 
 // z = clamp(sqrt(-2 ln(1 - ua)) cos(2 pi ub), -3, 3);  2^(0.2 z)
 __device__ __forceinline__ float dg_lognormal(float ua, float ub) {
@@ -50,39 +46,6 @@ __global__ __launch_bounds__(DG_BLOCK) void ada_geom_matrix_kernel(const float* 
     m[4] = __fmul_rn(c, sx); m[5] = __fmul_rn(-sn, sy); m[6] = __fmul_rn(sn, sx); m[7] = __fmul_rn(c, sy);
 }
 
-struct DgMat { float i00, i01, i10, i11, t00, t01, t10, t11; };
-
-__device__ __forceinline__ DgMat dg_load_mat(const float* __restrict__ m) {
-    DgMat q;
-    q.i00 = m[0]; q.i01 = m[1]; q.i10 = m[2]; q.i11 = m[3]; q.t00 = m[4]; q.t01 = m[5]; q.t10 = m[6]; q.t11 = m[7];
-    return q;
-}
-
-__device__ __forceinline__ bool dg_identity(const DgMat& q) {
-    return q.i00 == 1.f && q.i01 == 0.f && q.i10 == 0.f && q.i11 == 1.f && q.t00 == 1.f && q.t01 == 0.f && q.t10 == 0.f && q.t11 == 1.f;
-}
-
-// s_p = c + T^-1 (p - c) for the output pixel p = (column j, row i): THE position expression of the forward and the adjoint.
-__device__ __forceinline__ void geom_pos(const DgMat& q, float cx, float cy, int i, int j, float& sx, float& sy) {
-    const float dx = __fsub_rn((float)j, cx), dy = __fsub_rn((float)i, cy);
-    sx = __fadd_rn(cx, __fadd_rn(__fmul_rn(q.i00, dx), __fmul_rn(q.i01, dy)));
-    sy = __fadd_rn(cy, __fadd_rn(__fmul_rn(q.i10, dx), __fmul_rn(q.i11, dy)));
-}
-
-// w(s, t) = max(0, 1 - |s_x - t_x|) max(0, 1 - |s_y - t_y|): THE weight expression of the forward and the adjoint.
-__device__ __forceinline__ float geom_w(float sx, float sy, int tx, int ty) {
-    const float wx = fmaxf(0.f, __fsub_rn(1.f, fabsf(__fsub_rn(sx, (float)tx))));
-    const float wy = fmaxf(0.f, __fsub_rn(1.f, fabsf(__fsub_rn(sy, (float)ty))));
-    return __fmul_rn(wx, wy);
-}
-
-__device__ __forceinline__ void dg_acc(float (&acc)[3], float w, const float* __restrict__ px) {
-    const f32x3u v = *reinterpret_cast<const f32x3u*>(px);
-    acc[0] = __fadd_rn(acc[0], __fmul_rn(w, v.x));
-    acc[1] = __fadd_rn(acc[1], __fmul_rn(w, v.y));
-    acc[2] = __fadd_rn(acc[2], __fmul_rn(w, v.z));
-}
-
 // Forward value of output pixel (i, j): taps in the order (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1), those outside the image
 // skipped.  A position far outside (|s| beyond the int range cannot occur: |T^-1| <= 2.3 and the image is < 2^31 / 3 floats).
 __device__ __forceinline__ void dg_fwd_px(const float* __restrict__ xb, int H, int W, const DgMat& q, float cx, float cy, int i, int j,
@@ -102,40 +65,11 @@ __device__ __forceinline__ void dg_fwd_px(const float* __restrict__ xb, int H, i
     }
 }
 
-// Adjoint value of pixel q = (row qi, column qj): the candidates p are the integers of the box centre +- (extent + margin), centre
-// = c + T (q - c), extent = (|t00| + |t01|, |t10| + |t11|); nx, ny (the trip counts) come from the matrix alone.  Candidates are
-// visited row by row, those with a zero weight or outside the image skipped.
+// Adjoint value of pixel q = (row qi, column qj): the candidate walk of dg_adj_walk (adageom.h) from +0.
 __device__ __forceinline__ void dg_adj_px(const float* __restrict__ gb, int H, int W, const DgMat& q, float cx, float cy, float ex, float ey,
                                           int nx, int ny, int qi, int qj, float (&acc)[3]) {
-    const float dx = (float)qj - cx, dy = (float)qi - cy;
-    const float px = cx + (q.t00 * dx + q.t01 * dy), py = cy + (q.t10 * dx + q.t11 * dy);
     acc[0] = acc[1] = acc[2] = 0.f;
-    if (!(px > -8.f && px < (float)W + 8.f && py > -8.f && py < (float)H + 8.f)) return;      // the whole box is outside
-    const int j0 = (int)ceilf(px - ex), i0 = (int)ceilf(py - ey);
-    for (int di = 0; di < ny; ++di) {
-        const int i = i0 + di;
-        if (i < 0 || i >= H) continue;
-        for (int dj = 0; dj < nx; ++dj) {
-            const int j = j0 + dj;
-            if (j < 0 || j >= W) continue;
-            float sx, sy;
-            geom_pos(q, cx, cy, i, j, sx, sy);
-            const float w = geom_w(sx, sy, qj, qi);
-            if (w > 0.f) dg_acc(acc, w, gb + ((size_t)i * W + j) * 3);
-        }
-    }
-}
-
-struct DgBox { float ex, ey; int nx, ny; };                     // the adjoint's candidate box: half extents (with the slack) and trip counts
-
-template <bool ADJ>
-__device__ __forceinline__ DgBox dg_box(const DgMat& q) {
-    DgBox bx = {0.f, 0.f, 0, 0};
-    if (ADJ) {
-        bx.ex = fabsf(q.t00) + fabsf(q.t01) + DG_MARGIN; bx.ey = fabsf(q.t10) + fabsf(q.t11) + DG_MARGIN;
-        bx.nx = min((int)floorf(2.f * bx.ex) + 1, 7); bx.ny = min((int)floorf(2.f * bx.ey) + 1, 7);
-    }
-    return bx;
+    dg_adj_walk(gb, H, W, q, cx, cy, ex, ey, nx, ny, qi, qj, acc);
 }
 
 // Any H, W, any 4-byte aligned base: one pixel per thread in row order, one trip (short-lived blocks).  grid (ceil(H W / DG_BLOCK), B).
@@ -170,9 +104,6 @@ __global__ __launch_bounds__(DG_BLOCK) void ada_geom_px_kernel(const float* __re
 // 11 times the blit tile kernel's.  An identity image is copied in row order, four pixels (three 16-byte loads
 // and stores) per thread: the grid's DG_TILE^2-pixel tiles are at least as many as its DG_TILE^2-pixel runs.
 // grid (ceil(H / DG_TILE) * ceil(W / DG_TILE), B).
-constexpr int DG_TILE = 32;
-static_assert(DG_TILE * DG_TILE == 4 * DG_BLOCK && DG_TILE == 4 * 8 && DG_BLOCK == 4 * WAVE, "four waves of eight rows, four 8 x 8 patches each");
-
 template <bool ADJ>
 __global__ __launch_bounds__(DG_BLOCK) void ada_geom_tile_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ mat,
                                                                  int H, int W, int tiles_x) {

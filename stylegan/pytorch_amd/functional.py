@@ -2678,14 +2678,19 @@ def ada_geom_matrix(u, bits, gu=None, state=None):
     return _ada_matrix(_STAGE["geom"], u, bits, gu, state)
 
 
-def _ada_geom(x, mat, adjoint):
+def _ada_geom(x, mat, adjoint, entry="sgx_ada_geom"):
     x, mat, y = _ada_table_pass("geom", x, mat)
     B, H, W, _ = x.shape
-    N.check(N.lib().sgx_ada_geom(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), N.stream()), "sgx_ada_geom")
+    N.check(getattr(N.lib(), entry)(N.ptr(x), N.ptr(y), N.ptr(mat), B, H, W, int(adjoint), N.stream()), entry)
     return y
 
 
 AdaGeomFn, AdaGeomAdjFn = _adjoint_chain("AdaGeom", lambda x, adjoint, with_bias, mat: _ada_geom(x, mat, adjoint), 1, lin=False)
+# The same resample with the paper's reflection padding (``sgx_ada_geom_reflect``; Discriminator(geom_padding="reflect")): the same
+# table, linear as well, so the pair is each other's backward and the R1 double backward is the forward kernel again.
+GEOM_PADDINGS = {"zeros": "AdaGeomFn", "reflect": "AdaGeomReflectFn"}
+AdaGeomReflectFn, AdaGeomReflectAdjFn = _adjoint_chain(
+    "AdaGeomReflect", lambda x, adjoint, with_bias, mat: _ada_geom(x, mat, adjoint, "sgx_ada_geom_reflect"), 1, lin=False)
 
 
 # The colour group of the ADA paper (brightness, contrast, lumaflip, hue, saturation; ``sgx_ada_color_matrix`` / ``sgx_ada_color``,

@@ -92,6 +92,8 @@ SIGNATURES = {
     "sgx_ada_gates_n": (I, [P, I, I, P, I, P, I, P]),
     "sgx_ada_geom_matrix": (I, [P, I, P, I, P, I, P, I, P]),
     "sgx_ada_geom": (I, [P, P, P, I, I, I, I, P]),
+    "sgx_ada_geom_reflect": (I, [P, P, P, I, I, I, I, P]),
+    "sgx_ada_geom_reflect_plan": (I, [I, I, I, I, I, P]),
     "sgx_ada_color_matrix": (I, [P, I, P, I, P, I, P, I, P]),
     "sgx_ada_color": (I, [P, P, P, I, I, I, I, I, P]),
     "sgx_ada_filter_matrix": (I, [P, I, P, I, P, I, P, I, P]),
